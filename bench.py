@@ -18,16 +18,27 @@ adds the reference's --flush option: 4 x 1 GB of fills between calls, outside th
 alpha = 1, beta = 0 (the driver's default), x/y = integers in [-20, 20) as fp64.
 GFLOP/s = 2 * stored nnz / t (stored zeros counted, like the reference's drivers).
 
-N = 1 also measures, under a time cap (--extras-seconds, default 150; 0 = off), the other SURVEY 8(d) metrics so that the
-driver's record holds them: "spmv_mv" = BASELINE config 3 (the same matrix x 16 right-hand sides, LayoutRight and
-LayoutLeft X / Y) and "spgemm" = the largest single-GPU member of config 4 (C = A*A on R-MAT scale 20, edge factor 16:
-symbolic, numeric, numeric reuse), each with its CPU baseline (OpenMP ports in oracle/, bounded samples).
-
-The JSON line also carries
+A plain run does only what the headline needs: set up, first call + W warm-ups, the K timed steps, the outputs if
+--dump-outputs is given, the JSON line.  The line carries
   roofline     algorithmic bytes of ONE local SpMV (nnz*12 + (rows+1)*4 + x touched*8 + rows*8)
-               / the SpMV's average duration measured with HIP events on the launch stream, vs 8 TB/s HBM3E;
-  cpu_baseline the OpenMP port of the reference's host SpMV (oracle/kk_oracle_omp.c) on a bounded sample
-               of the same workload, timed on this box's host cores (rank 0, N = 1 only).
+               / the step's own clock and / the SpMV's average duration measured with HIP events on the launch stream,
+               vs 8 TB/s HBM3E; memory-side traffic from the committed counter file when it matches the sources.
+
+--full adds everything else, each measured after the timed region:
+  roofline.measured_stream_read_GBps  the device's own streaming-read rate (N = 1);
+  the A*1 self-check of the matrix (every rank, through the exchange for N > 1);
+  exchange     N > 1 (or a named --exchange): every exchange the library has, step / exchange alone / local SpMV alone;
+  cpu_baseline the OpenMP port of the reference's host SpMV (oracle/kk_oracle_omp.c) on the same workload, timed on the
+               host cores (rank 0; --no-cpu-baseline drops it and the other CPU baselines);
+  N = 1, under a time cap (--extras-seconds, default 180; 0 = off), the other SURVEY 8(d) metrics: "spmv_mv" = BASELINE
+  config 3 (the same matrix x 16 right-hand sides, LayoutRight and LayoutLeft X / Y), "spmv_gather_bound",
+  "spmv_mv_off_lattice" and "spgemm" = the largest single-GPU member of config 4 (C = A*A on R-MAT scale 20, edge factor 16:
+  symbolic, numeric, numeric reuse), each with its CPU baseline (OpenMP ports in oracle/, bounded samples).
+
+--dump-outputs DIR writes y of the last timed step -- what a caller of the SpMV receives -- as float64 .npy files: y.npy
+(y_rank<r>.npy per rank for N > 1) holds a fixed, seeded sample of DUMP_SAMPLES rows over all ranks (the whole vector
+when it is smaller), y_rows.npy (y_rank<r>_rows.npy) the global row of every value.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -41,6 +52,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6.3 TB/s is what a plain copy reaches
 PMC_FILE = os.path.join(ROOT, "profiles", "round6", "bench_n1_pmc_hbm.json")
 MV_PMC_FILE = os.path.join(ROOT, "profiles", "round6", "mv4_pmc_hbm.json")
+DUMP_SAMPLES = 1 << 21   # rows of y that --dump-outputs writes over all ranks: 16 MB of values + 16 MB of row indices
 
 
 def kernel_source_sha(unit="kk_spmv.hip"):
@@ -97,6 +109,20 @@ def cpu_baseline(sample_n=300, min_seconds=6.0):
     return {"value": round(gflops, 3), "unit": "GFLOP/s", "cores": oracle.omp_threads(), "kind": "port",
             "sample": "%s: 27-pt FE Laplacian %d^3 (%d rows, %d nnz), fp64, OpenMP dynamic schedule (nnz > 1e7), %d iterations, %.1f algorithmic GB/s"
                       % (note, sample_n, A.nrows, A.nnz, it, gbps)}
+
+
+def dump_outputs(dirname, y, row0, rank, world):
+    """--dump-outputs: y of the last timed step as float64 .npy files -- every row when the vector holds at most its share of
+    DUMP_SAMPLES, else a fixed sample drawn from a seed of its own per rank -- and beside it the global row of every value"""
+    import numpy as np
+    import torch
+    n, k = int(y.shape[0]), DUMP_SAMPLES // world
+    rows = np.arange(n, dtype=np.int64) if n <= k else np.unique(np.random.default_rng(8128 + rank).integers(0, n, size=k))
+    vals = y[torch.from_numpy(rows).to(y.device)].to(torch.float64).cpu().numpy()
+    tag = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "y%s.npy" % tag), vals)
+    np.save(os.path.join(dirname, "y%s_rows.npy" % tag), (rows + row0).astype(np.float64))
 
 
 def _fenced(fn, sync, reps, flush=None):
@@ -449,11 +475,16 @@ def main():
     ap.add_argument("--beta", type=float, default=0.0)
     ap.add_argument("--algo", default="SPMV_DEFAULT")
     ap.add_argument("--knob", action="append", default=[], help="key=value expert knob for the SpMV plan")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: stream-read rate, A*1 self-check, every exchange, "
+                         "CPU baselines, and for N = 1 the spmv_mv / spmv_gather_bound / spmv_mv_off_lattice / spgemm sections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write y of the last timed step (a fixed, seeded sample of its rows) to DIR/*.npy as float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baselines")
     ap.add_argument("--no-fence", action="store_true", help="queue the K timed steps back to back (no per-call fence, no per-call times)")
     ap.add_argument("--flush", action="store_true", help="also report the per-call times with the reference's --flush (4 x 1 GB of fills between calls)")
     ap.add_argument("--extras-seconds", type=float, default=180.0,
-                    help="N = 1: time cap for the spmv_mv (config 3) and spgemm (config 4) sections of the line; 0 skips them")
+                    help="--full, N = 1: time cap for the spmv_mv (config 3) and spgemm (config 4) sections of the line; 0 skips them")
     ap.add_argument("--emulate", action="store_true",
                     help="debug / CI: run the whole flow on CPU -- gloo instead of RCCL, the kernels under the SIMT emulator of "
                          "tests/emu, a tiny grid -- to exercise the multi-process control flow without GPUs (numbers are meaningless)")
@@ -568,6 +599,8 @@ def main():
     t1 = time.perf_counter()
     ms_step = (t1 - t0) * 1e3 / args.steps
     kern_ms = sum(a.elapsed_time(b) for a, b in evs) / args.steps      # local SpMV kernels (N > 1 with overlap: incl. the wait for the halo)
+    if args.dump_outputs:                       # before anything below runs the SpMV again
+        dump_outputs(args.dump_outputs, y_shard, rank * rows_per_rank, rank, world)
 
     nnz_total = torch.tensor([float(nnz_local)], device=dev, dtype=torch.float64)
     pc_min, pc_max = (min(per_call), max(per_call)) if per_call else (0.0, 0.0)
@@ -588,7 +621,7 @@ def main():
     def all_reduce_(t, how):
         if dist is not None: dist.all_reduce(t, op=how)
     RED_MIN, RED_MAX = (dist.ReduceOp.MIN, dist.ReduceOp.MAX) if dist is not None else (None, None)
-    if use_dist:
+    if use_dist and args.full:
         def timed(fn, n=max(3, min(args.steps, 20))):
             fn(); barrier()
             t_ = time.perf_counter()
@@ -630,19 +663,20 @@ def main():
                 xchg[name]["form_us_at_creation"] = o.allgather_us
         ops.clear()
 
-    # ---- sanity inside the bench: A*1 over the slab must be the row-sum vector (0 interior, 1 boundary) ----
-    chk = torch.empty(rows_per_rank, dtype=torch.float64, device=dev)
-    if not use_dist:
-        ones = torch.ones(nrows_global, dtype=torch.float64, device=dev)
-        kk.spmv(handle, "N", 1.0, A, tb(ones), 0.0, tb(chk))
-    else:
-        x_keep = x_shard.clone(); x_shard.fill_(1.0)
-        op.apply(1.0, x_shard, 0.0, chk)               # through the exchange: every rank's halo must arrive as ones
-        x_shard.copy_(x_keep)
-    lens = A.graph.row_map[1:] - A.graph.row_map[:-1]
-    if emu:
-        lens = torch.from_numpy(np.asarray(lens))
-    assert bool((chk[lens == 27] == 0).all()) and bool((chk[lens < 27] == 1).all()), "bench self-check failed"
+    # ---- --full, sanity inside the bench: A*1 over the slab must be the row-sum vector (0 interior, 1 boundary) ----
+    if args.full:
+        chk = torch.empty(rows_per_rank, dtype=torch.float64, device=dev)
+        if not use_dist:
+            ones = torch.ones(nrows_global, dtype=torch.float64, device=dev)
+            kk.spmv(handle, "N", 1.0, A, tb(ones), 0.0, tb(chk))
+        else:
+            x_keep = x_shard.clone(); x_shard.fill_(1.0)
+            op.apply(1.0, x_shard, 0.0, chk)               # through the exchange: every rank's halo must arrive as ones
+            x_shard.copy_(x_keep)
+        lens = A.graph.row_map[1:] - A.graph.row_map[:-1]
+        if emu:
+            lens = torch.from_numpy(np.asarray(lens))
+        assert bool((chk[lens == 27] == 0).all()) and bool((chk[lens < 27] == 1).all()), "bench self-check failed"
 
     # ---- roofline of the dominant kernel (local SpMV) -------------------------------------------
     if world == 1:
@@ -696,8 +730,8 @@ def main():
         except Exception:
             pass
         # The device's own streaming-read rate next to the 8 TB/s spec ("re-measure on the build box and quote both"): the
-        # matrix values (5.8 GB on C2) through kkamd_bench_read -- 16-byte loads, 256 lanes, 4 independent loads in flight per lane.
-        if world == 1 and not emu:
+        # matrix values (5.8 GB on C2) through kkamd_bench_read -- 16-byte loads, 256 lanes, 4 independent loads in flight per lane (--full).
+        if world == 1 and not emu and args.full:
             try:
                 vals_ = A.values; nbytes_ = int(vals_.numel() * vals_.element_size()) // 16 * 16
                 sink_ = torch.zeros(8, dtype=torch.float64, device=dev)
@@ -748,13 +782,13 @@ def main():
             out["per_call_ms_flushed"] = flushed
         if xchg is not None:
             out["exchange"] = xchg
-        if emu:       # control-flow check: the same leg on the emulated grid (a fraction of a second)
+        if args.full and emu:       # control-flow check: the same leg on the emulated grid (a fraction of a second)
             out["cpu_baseline"] = cpu_baseline(sample_n=n, min_seconds=0.2)
             out["cpu_baseline"]["sample"] = "EMULATED RUN, tiny grid: " + out["cpu_baseline"]["sample"]
-        elif not args.no_cpu_baseline:     # every GPU count (north_star: the host path "in the same run"); rank 0, after the timed region
+        elif args.full and not args.no_cpu_baseline:     # every GPU count (north_star: the host path "in the same run"); rank 0, after the timed region
             out["cpu_baseline"] = cpu_baseline()
-        # ---- the other SURVEY 8(d) metrics, driver-visible: config 3 (SpMV_MV) and config 4 (SpGEMM), each under its share of the cap
-        if not use_dist and not emu and not args.n and args.extras_seconds > 0:
+        # ---- --full: the other SURVEY 8(d) metrics, driver-visible: config 3 (SpMV_MV) and config 4 (SpGEMM), each under its share of the cap
+        if args.full and not use_dist and not emu and not args.n and args.extras_seconds > 0:
             t_x = time.perf_counter()
             del x_shard, y_shard, chk
             try:

@@ -3,6 +3,7 @@ as the product, compiled by g++ against the SIMT emulator (kk_emu.h).  Lets `-m 
 kernel logic (tiling, carries, hash tables, scans, sorts) on a machine without a GPU.  It is NOT a CPU
 fallback of the product: nothing under kokkos-kernels_amd/ can load it."""
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -12,11 +13,16 @@ import kk_loader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "libkkamd_emu.so")
+LOCK = os.path.join(HERE, ".build.lock")
 _BACKEND = None
 
 
 def build():
-    subprocess.check_call(["make", "-C", HERE, "-s"])
+    # several processes may ask at once (the ranks of a multi-process test): one runs make, the others wait for it and find
+    # the library up to date, instead of writing the same objects concurrently
+    with open(LOCK, "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        subprocess.check_call(["make", "-C", HERE, "-s"])
     return SO
 
 

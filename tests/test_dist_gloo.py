@@ -211,11 +211,11 @@ def test_bench_two_process_flow_emulated(launcher):
     (`python bench.py --gpus 2`: no WORLD_SIZE in the environment, bench.py launches its own ranks), with
     --emulate: gloo instead of RCCL and the kernels under the SIMT emulator.  Checks the whole multi-process control
     flow -- slab generation, halo plan, interior/boundary overlap, barriers, max-over-ranks timing, the A*1 self-check,
-    the single JSON line from rank 0 -- without a GPU."""
+    the single JSON line from rank 0 -- without a GPU.  --full: the line carries the host baseline and every exchange."""
     import json
     import subprocess
     port = 29900 + (os.getpid() % 500)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--emulate", "--grid-edge", "32"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--emulate", "--grid-edge", "32", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)] + tail
     else:

@@ -3,7 +3,8 @@ REFERENCE's own headers: the integration step is performed on copies of the refe
 directory, and `g++ -fsyntax-only` parses the reference's sparse/impl/*_spec.hpp with them over a declarations-only stand-in
 for Kokkos core (tests/kokkos_mock/).  The translation units assert that every claimed type tuple -- built the way the public
 KokkosSparse::spmv / spgemm_* build their internal types -- selects the KKAMD specialisation.
-Needs /root/reference (present in the build container, absent on the GPU box): skipped without it."""
+The reference's headers are read from oracle/_ref/kokkos-kernels/, where __graft_entry__.build() stages them from a checkout of the
+reference (oracle/ref_headers.py); skipped when build() found none to stage."""
 import os
 import shutil
 import subprocess
@@ -11,7 +12,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+REF = os.path.join(ROOT, "oracle", "_ref", "kokkos-kernels")       # staged by build(): oracle/ref_headers.py
 TPL = os.path.join(ROOT, "kokkos-kernels_amd", "host", "kokkos_tpl")
 MOCK = os.path.join(ROOT, "tests", "kokkos_mock")
 GENERATED = ["KokkosSparse_spmv_eti_spec_avail.hpp", "KokkosSparse_spmv_mv_eti_spec_avail.hpp", "KokkosSparse_spmv_eti_spec_decl.hpp",
@@ -19,7 +20,7 @@ GENERATED = ["KokkosSparse_spmv_eti_spec_avail.hpp", "KokkosSparse_spmv_mv_eti_s
              "KokkosSparse_spgemm_symbolic_eti_spec_decl.hpp", "KokkosSparse_spgemm_numeric_eti_spec_avail.hpp",
              "KokkosSparse_spgemm_numeric_eti_spec_decl.hpp"]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sparse", "tpls")), reason="the reference checkout is not on this machine")
+pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "sparse", "tpls")), reason="no reference headers in oracle/_ref (build() found no checkout of the reference to stage)")
 
 
 def integrate(tmp):

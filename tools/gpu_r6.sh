@@ -8,12 +8,12 @@ echo "== box: $(rocminfo 2>/dev/null | grep -m1 -E 'gfx9[0-9a-z]+') cpus $(nproc
 if has probe;  then ./tools/probes/probe_mfma_f64 > $OUT/probe_mfma_f64.txt 2>&1; echo "probe rc=$?"; head -12 $OUT/probe_mfma_f64.txt; fi
 if has probelds; then ./tools/probes/probe_lds > $OUT/probe_lds.txt 2>&1; echo "probe_lds rc=$?"; cat $OUT/probe_lds.txt; fi
 if has rccl; then timeout 600 python -m pytest tests -m gpu -x -q -rA -k "rccl or loopback or two_processes" > $OUT/pytest_rccl.log 2>&1; echo "rccl pytest rc=$?"; tail -8 $OUT/pytest_rccl.log
-  timeout 600 python bench.py --gpus 1 --exchange allgather --steps 20 --no-cpu-baseline > $OUT/bench_n1_allgather.json 2> $OUT/bench_n1_allgather.err; echo "bench --gpus 1 --exchange allgather rc=$?"; tail -2 $OUT/bench_n1_allgather.err; cat $OUT/bench_n1_allgather.json; fi
+  timeout 600 python bench.py --gpus 1 --exchange allgather --steps 20 --full --no-cpu-baseline > $OUT/bench_n1_allgather.json 2> $OUT/bench_n1_allgather.err; echo "bench --gpus 1 --exchange allgather rc=$?"; tail -2 $OUT/bench_n1_allgather.err; cat $OUT/bench_n1_allgather.json; fi
 if has abc3; then for i in 1 2 3; do for t in build/r3:round3 .:head; do timeout 300 python tools/ab_c3.py ${t%%:*} ${t##*:} >> $OUT/ab_c3.jsonl 2>> $OUT/ab_c3.err; done; done; echo "abc3 rc=$?"; cat $OUT/ab_c3.jsonl; fi
 if has pytestk; then timeout ${PYTEST_TIMEOUT:-1500} python -m pytest tests -m gpu -x -q -k "$PYTEST_K" > $OUT/pytest_gpu_k.log 2>&1; echo "pytest -k rc=$?"; tail -6 $OUT/pytest_gpu_k.log; fi
 if has pytest; then timeout ${PYTEST_TIMEOUT:-1500} python -m pytest tests -m gpu -x -q -rA > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|error" $OUT/pytest_gpu.log | tail -5; grep -E "^(FAILED|ERROR)" $OUT/pytest_gpu.log | head; fi
 if has pytestfast; then KK_SKIP_HEAVY=1 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu_fast.log 2>&1; echo "pytest(fast) rc=$?"; tail -4 $OUT/pytest_gpu_fast.log; fi
-if has bench;  then timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err; cat $OUT/bench.json; fi
+if has bench;  then timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err; cat $OUT/bench.json; fi
 if has mv3;    then timeout 900 python tools/bench_mv3.py 300 ${MV3_ARGS:-} > $OUT/bench_mv3.jsonl 2> $OUT/bench_mv3.err; echo "mv3 rc=$?"; tail -3 $OUT/bench_mv3.err; cat $OUT/bench_mv3.jsonl; fi
 if has mv4;    then timeout 900 python tools/bench_mv4.py 300 ${MV4_ARGS:-} > $OUT/bench_mv4.jsonl 2> $OUT/bench_mv4.err; echo "mv4 rc=$?"; tail -3 $OUT/bench_mv4.err; cat $OUT/bench_mv4.jsonl; fi
 if has extra;  then timeout ${EXTRA_TIMEOUT:-900} bash -c "$EXTRA_CMD" > $OUT/extra.log 2>&1; echo "extra rc=$?"; tail -${EXTRA_TAIL:-40} $OUT/extra.log; fi
