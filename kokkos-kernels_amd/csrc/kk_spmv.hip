@@ -1970,6 +1970,9 @@ int kkamd_spmv(kkamd_spmv_plan_t* plan, const kkamd_crs_t* A, char mode, double 
   if ((rc = kk::check_plan(plan, A))) return rc;
   if (vector_type != KKAMD_F32 && vector_type != KKAMD_F64)
     return kk::fail(KKAMD_ERR_UNSUPPORTED, "kkamd_spmv: unsupported vector_type %d", vector_type);
+  // the pairs KK_DISPATCH_TYPES runs, checked before the alpha == 0 / empty-matrix shortcut: a pair is refused whatever alpha and A are
+  if (A->value_type == KKAMD_F64 && vector_type != KKAMD_F64)
+    return kk::fail(KKAMD_ERR_UNSUPPORTED, "kkamd_spmv: unsupported (value,vector) type pair (%d,%d)", A->value_type, vector_type);
   hipStream_t st     = kk::to_hip(stream);
   const int64_t ylen = trans ? A->num_cols : A->num_rows;
   const int64_t xlen = trans ? A->num_rows : A->num_cols;

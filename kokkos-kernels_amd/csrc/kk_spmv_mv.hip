@@ -1320,6 +1320,8 @@ int kkamd_spmv_mv(kkamd_spmv_plan_t* plan, const kkamd_crs_t* A, char mode, doub
   if (nvec < 0) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spmv_mv: negative number of vectors");
   if (vector_type != KKAMD_F32 && vector_type != KKAMD_F64)
     return kk::fail(KKAMD_ERR_UNSUPPORTED, "kkamd_spmv_mv: unsupported vector_type %d", vector_type);
+  if (A->value_type == KKAMD_F64 && vector_type != KKAMD_F64)                  // before the shortcuts below, as in kkamd_spmv
+    return kk::fail(KKAMD_ERR_UNSUPPORTED, "kkamd_spmv_mv: unsupported (value,vector) type pair (%d,%d)", A->value_type, vector_type);
   hipStream_t st     = kk::to_hip(stream);
   const int64_t ylen = trans ? A->num_cols : A->num_rows;
   if (nvec == 0 || ylen == 0) return KKAMD_OK;

@@ -153,8 +153,11 @@ void spmv_struct(const ExecutionSpace& space, const char mode[], const int stenc
       KokkosKernels::Impl::throw_runtime_exception(os.str());
     }
   }
-  if (x.stride(0) != 1 || y.stride(0) != 1) {     // strided rank-1 views: the unstructured path handles them
-    KokkosSparse::spmv(space, mode, alpha, A, x, beta, y);
+  if (x.stride(0) != 1 || y.stride(0) != 1) {     // strided rank-1 views: the unstructured path handles them, on their leading
+    const bool tr   = !((mode[0] == NoTranspose[0]) || (mode[0] == Conjugate[0]));   // numCols / numRows elements (spmv wants exact lengths)
+    const int n_in  = (int)(tr ? A.numRows() : A.numCols());
+    const int n_out = (int)(tr ? A.numCols() : A.numRows());
+    KokkosSparse::spmv(space, mode, alpha, A, Kokkos::subview(x, Kokkos::make_pair(0, n_in)), beta, Kokkos::subview(y, Kokkos::make_pair(0, n_out)));
     return;
   }
   kkamd_crs_t desc = Impl::make_crs_desc(A);

@@ -248,7 +248,12 @@ template <class T, class... P> View<T*, P...> subview(const View<T**, P...>& v, 
 template <class T, class... P> View<T**, P...> subview(const View<T**, P...>& v, ALL_t, std::pair<int, int> r) {
   return View<T**, P...>(v.data() + (size_t)r.first * v.stride(1), v.extent(0), (size_t)(r.second - r.first), v.stride(0), v.stride(1));
 }
+// elements [i0, i1) of a rank-1 view (its stride kept)
+template <class T, class... P> View<T*, P...> subview(const View<T*, P...>& v, std::pair<int, int> r) {
+  return View<T*, P...>(v.data() + (size_t)r.first * v.stride(0), (size_t)(r.second - r.first), 1, v.stride(0), (size_t)(r.second - r.first));
+}
 template <class A, class B> using pair = std::pair<A, B>;
+template <class A, class B> std::pair<A, B> make_pair(A a, B b) { return std::pair<A, B>(a, b); }
 
 }  // namespace Kokkos
 

@@ -9,6 +9,7 @@
 // Expected values come from the test's own sequential loops, as in the reference's tests.
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <limits>
 #include <random>
 #include "KokkosSparse_spmv.hpp"
@@ -533,6 +534,103 @@ void test_dist_single_rank() {
   EXPECT(ok);
 }
 
+// Kokkos code passes subviews all the time: columns [1, 6) of a LayoutRight / LayoutLeft multivector (the reference's check_spmv_mv
+// runs on such subviews, Test_Sparse_spmv.hpp:244-251) and a single column as a (strided) rank-1 vector; the parents' other columns
+// must come back bit-identical.  Whole parents travel to and from the host (deep_copy takes contiguous views only).
+template <class layout>
+void test_subviews() {
+  std::vector<int> rm, ent; std::vector<double> val;
+  const int m = 111, n = 99, nc = 8;
+  auto A = make_random<double, int>(m, n, 5, rm, ent, val, 4242);
+  const bool right = std::is_same<layout, Kokkos::LayoutRight>::value;
+  auto at = [&](int i, int c, int rows) { return right ? (size_t)i * nc + c : (size_t)c * rows + i; };
+  std::mt19937 g(977);
+  std::vector<double> hX(n * nc), hY(m * nc);
+  for (auto& v : hX) v = (g() % 1000) / 1000.0;
+  for (auto& v : hY) v = (g() % 1000) / 1000.0;
+  const double alpha = 1.5, beta = -0.5;
+  auto rowsum = [&](int r, int cx) { double s = 0; for (int q = rm[r]; q < rm[r + 1]; ++q) s += val[q] * hX[at(ent[q], cx, n)]; return s; };
+  Kokkos::View<double**, layout, device> X("X", n, nc), Y("Y", m, nc);
+  Kokkos::deep_copy(X, Kokkos::View<double**, layout, Kokkos::HostSpace>(hX.data(), n, nc));
+  auto Y_h = Kokkos::create_mirror_view(Y);
+  // ycol(c) = the column of X that Y's column c was computed from, -1 = untouched
+  auto check = [&](const std::vector<int>& xcol) {
+    Kokkos::deep_copy(Y_h, Y);
+    double e = 0; bool guard = true;
+    for (int i = 0; i < m; ++i)
+      for (int c = 0; c < nc; ++c) {
+        const double old = hY[at(i, c, m)], got = Y_h(i, c);
+        if (xcol[c] < 0) guard = guard && std::memcmp(&old, &got, sizeof(double)) == 0;
+        else e = std::max(e, std::fabs(got - (beta * old + alpha * rowsum(i, xcol[c]))));
+      }
+    EXPECT(guard);
+    EXPECT(e < 1e-12);
+    Kokkos::deep_copy(Y, Kokkos::View<double**, layout, Kokkos::HostSpace>(hY.data(), m, nc));
+  };
+  Kokkos::deep_copy(Y, Kokkos::View<double**, layout, Kokkos::HostSpace>(hY.data(), m, nc));
+  auto Xs = Kokkos::subview(X, Kokkos::ALL(), Kokkos::make_pair(1, 6));
+  auto Ys = Kokkos::subview(Y, Kokkos::ALL(), Kokkos::make_pair(1, 6));
+  KokkosSparse::spmv("N", alpha, A, Xs, beta, Ys);
+  check({-1, 1, 2, 3, 4, 5, -1, -1});
+  KokkosSparse::SPMVHandle<device, decltype(A), decltype(Xs), decltype(Ys)> h(KokkosSparse::SPMV_DEFAULT);
+  for (int rep = 0; rep < 2; ++rep) { KokkosSparse::spmv(&h, "N", alpha, A, Xs, beta, Ys); check({-1, 1, 2, 3, 4, 5, -1, -1}); }
+  // one column as a rank-1 vector (stride nc in LayoutRight)
+  auto x1 = Kokkos::subview(X, Kokkos::ALL(), 2);
+  auto y1 = Kokkos::subview(Y, Kokkos::ALL(), 5);
+  KokkosSparse::spmv("N", alpha, A, x1, beta, y1);
+  check({-1, -1, -1, -1, -1, 2, -1, -1});
+  KokkosSparse::SPMVHandle<device, decltype(A), decltype(x1), decltype(y1)> h1(KokkosSparse::SPMV_DEFAULT);
+  KokkosSparse::spmv(&h1, "N", alpha, A, x1, beta, y1);
+  check({-1, -1, -1, -1, -1, 2, -1, -1});
+}
+
+// spmv_struct on a column of a LayoutRight multivector (stride 3) that is longer than the matrix: the unstructured path on the
+// leading numCols / numRows elements, the other columns and the extra rows untouched
+void test_spmv_struct_strided() {
+  const int ni = 23, nj = 9, n = ni * nj, extra = 4, nc = 3;
+  std::vector<int> rm(n + 1, 0), ent; std::vector<double> val;
+  for (int j = 0; j < nj; ++j)
+    for (int i = 0; i < ni; ++i) {
+      const int r = j * ni + i;
+      if (i == 0 || j == 0 || i == ni - 1 || j == nj - 1) { ent.push_back(r); val.push_back(1.0); }
+      else { const int c[5] = {r - ni, r - 1, r, r + 1, r + ni}; for (int q = 0; q < 5; ++q) { ent.push_back(c[q]); val.push_back(q == 2 ? 4.0 : -1.0 - 0.25 * q); } }
+      rm[r + 1] = (int)ent.size();
+    }
+  using M = KokkosSparse::CrsMatrix<double, int, device, void, int>;
+  typename M::row_map_type::non_const_type d_rm("rm", n + 1);
+  typename M::index_type d_ent("ent", ent.size());
+  typename M::values_type d_val("val", val.size());
+  Kokkos::deep_copy(d_rm, Kokkos::View<int*, Kokkos::HostSpace>(rm.data(), rm.size()));
+  Kokkos::deep_copy(d_ent, Kokkos::View<int*, Kokkos::HostSpace>(ent.data(), ent.size()));
+  Kokkos::deep_copy(d_val, Kokkos::View<double*, Kokkos::HostSpace>(val.data(), val.size()));
+  M A("A", n, n, ent.size(), d_val, d_rm, d_ent);
+  Kokkos::View<int*, Kokkos::HostSpace> structure("structure", 2);
+  structure(0) = ni; structure(1) = nj;
+  const int rows = n + extra;
+  std::mt19937 g(31);
+  std::vector<double> hX(rows * nc), hY(rows * nc);
+  for (auto& v : hX) v = (g() % 1000) / 1000.0;
+  for (auto& v : hY) v = (g() % 1000) / 1000.0;
+  Kokkos::View<double**, Kokkos::LayoutRight, device> X("X", rows, nc), Y("Y", rows, nc);
+  Kokkos::deep_copy(X, Kokkos::View<double**, Kokkos::LayoutRight, Kokkos::HostSpace>(hX.data(), rows, nc));
+  Kokkos::deep_copy(Y, Kokkos::View<double**, Kokkos::LayoutRight, Kokkos::HostSpace>(hY.data(), rows, nc));
+  const double alpha = 1.5, beta = 0.5;
+  KokkosSparse::Experimental::spmv_struct("N", 1, structure, alpha, A, Kokkos::subview(X, Kokkos::ALL(), 1), beta, Kokkos::subview(Y, Kokkos::ALL(), 1));
+  auto Y_h = Kokkos::create_mirror_view(Y);
+  Kokkos::deep_copy(Y_h, Y);
+  double e = 0; bool guard = true;
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < nc; ++c) {
+      const double old = hY[r * nc + c], got = Y_h(r, c);
+      if (c != 1 || r >= n) { guard = guard && std::memcmp(&old, &got, sizeof(double)) == 0; continue; }
+      double s = 0;
+      for (int q = rm[r]; q < rm[r + 1]; ++q) s += val[q] * hX[ent[q] * nc + 1];
+      e = std::max(e, std::fabs(got - (beta * old + alpha * s)));
+    }
+  EXPECT(guard);
+  EXPECT(e < 1e-12);
+}
+
 int main() {
   Kokkos::initialize();
   test_dist_single_rank();
@@ -542,6 +640,9 @@ int main() {
   test_github_issue_101();
   test_all_interfaces<Kokkos::LayoutLeft>();
   test_all_interfaces<Kokkos::LayoutRight>();
+  test_subviews<Kokkos::LayoutLeft>();
+  test_subviews<Kokkos::LayoutRight>();
+  test_spmv_struct_strided();
   test_spgemm<int>();
   test_spgemm<size_t>();
   Kokkos::finalize();

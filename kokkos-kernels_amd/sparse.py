@@ -181,6 +181,17 @@ def _strides(a):
     return tuple(s // a.itemsize for s in a.strides)
 
 
+def _vec_stride(v, who):
+    """element stride of a rank-1 vector; 1 for a vector of at most one element (its stride is never used).  The C ABI
+    takes positive strides only: a reversed (negative) or broadcast (zero) view is refused here"""
+    if v.shape[0] <= 1:
+        return 1
+    s = _strides(v)[0]
+    if s <= 0:
+        raise RuntimeError("KokkosSparse::%s: vector stride %d is not supported (positive strides only)" % (who, s))
+    return s
+
+
 def spmv(*args):
     """KokkosSparse::spmv.  spmv(mode, alpha, A, x, beta, y) or spmv(handle, mode, alpha, A, x, beta, y)
     (the execution-space overloads map to the backend's current stream).  x, y rank 1 or rank 2.
@@ -207,8 +218,15 @@ def spmv(*args):
     d = A.desc()
     vt = _scalar_type(y)
     if len(x.shape) == 1:
-        check(lib, lib.kkamd_spmv(plan, C.byref(d), mode[0].encode(), float(alpha), be.ptr(x), float(beta), be.ptr(y),
-                                  vt, be.stream()))
+        xs, ys = _vec_stride(x, "spmv"), _vec_stride(y, "spmv")
+        if xs == 1 and ys == 1:
+            check(lib, lib.kkamd_spmv(plan, C.byref(d), mode[0].encode(), float(alpha), be.ptr(x), float(beta), be.ptr(y),
+                                      vt, be.stream()))
+        else:
+            # a strided rank-1 view (a column of a row-major multivector, a slice with a step): one column of the rank-2
+            # path, in place (as host/KokkosSparse_spmv.hpp does for strided Kokkos views)
+            check(lib, lib.kkamd_spmv_mv(plan, C.byref(d), mode[0].encode(), float(alpha), be.ptr(x), xs, xr,
+                                         float(beta), be.ptr(y), ys, yr, 1, vt, be.stream()))
     else:
         xs, ys = _strides(x), _strides(y)
         check(lib, lib.kkamd_spmv_mv(plan, C.byref(d), mode[0].encode(), float(alpha), be.ptr(x), xs[0], xs[1],
@@ -238,9 +256,15 @@ def spmv_struct(mode, stencil_type, structure, alpha, A, x, beta, y):
         if xc != 1:
             return spmv(mode, alpha, A, x, beta, y)
         xs, ys = _strides(x), _strides(y)
-        if xs[0] != 1 or ys[0] != 1:
-            return spmv(mode, alpha, A, x, beta, y)
-    st = (C.c_int64 * len(structure))(*[int(v) for v in structure])
+        strided = xs[0] != 1 or ys[0] != 1
+    else:
+        strided = _vec_stride(x, "spmv_struct") != 1 or _vec_stride(y, "spmv_struct") != 1
+    if strided:
+        # strided vectors take the unstructured path, on their leading numCols / numRows elements (they may be longer)
+        nin, nout = (m, n) if trans else (n, m)
+        spmv(mode, alpha, A, x[:nin], beta, y[:nout])
+        return y
+    st =(C.c_int64 * len(structure))(*[int(v) for v in structure])
     d = A.desc()
     check(lib, lib.kkamd_spmv_struct(C.byref(d), mode[0].encode(), int(stencil_type), len(structure), st, float(alpha),
                                      be.ptr(x), float(beta), be.ptr(y), _scalar_type(y), be.stream()))

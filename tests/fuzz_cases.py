@@ -24,6 +24,15 @@ def hubby(rng, n, ncols, base, nhubs, hublen, sort=True):
     return oracle.Crs(n, ncols, rm, ent, 1 + 49 * rng.random(rm[-1]))
 
 
+def mv_draw(rng):
+    """the rank-2 draws' types and view: fp32 vectors (with fp32 values) about 30 % of the time, an fp32 matrix with fp64 vectors about
+    20 %, X and Y as windows of padded parents (outside cells guarded) about half the time"""
+    r = rng.random()
+    vt, yt = (np.float32, np.float32) if r < 0.3 else ((np.float32, np.float64) if r < 0.5 else (None, np.float64))
+    view = str(rng.choice(pc.VIEWS)) if rng.random() < 0.5 else None
+    return {"value_dtype": vt, "vec_dtype": yt, "view": view}
+
+
 def run(be, budget, seed0=0, max_cases=None, kinds=None):
     """runs random cases until `budget` seconds are over (or max_cases); returns (cases passed, per-kind counts, last seed).
     kinds: only these kinds (indices into KINDS) are run, the others' seeds are skipped"""
@@ -71,7 +80,7 @@ def run(be, budget, seed0=0, max_cases=None, kinds=None):
                     pc.check_spmv_mv(be, M, int(rng.choice([2, 5, 16, 16, 21, 32])), mode, float(rng.integers(-3, 4)), beta, str(rng.choice(["C", "F"])), str(rng.choice(["C", "F"])),
                                      algo="SPMV_DEFAULT", seed=case, max_val=50.0, nans=(beta == 0.0 and rng.random() < 0.5), offset_dtype=odt,
                                      knobs={"mv6": int(rng.choice([0, 1, 2, 2])), "explicit_transpose_min_knnz": 0, "explicit_transpose": int(rng.choice([0, 1, 1])),
-                                            "values_tracking": int(rng.integers(0, 3))})
+                                            "values_tracking": int(rng.integers(0, 3))}, **mv_draw(rng))
             elif kind == 4:    # sort / merge / transpose
                 M = hubby(rng, int(rng.integers(5, 300)), int(rng.integers(50, 40000)), int(rng.integers(1, 30)), int(rng.integers(0, 3)), int(rng.integers(9000, 40000)), sort=False)
                 M.entries[rng.integers(0, M.nnz, size=M.nnz // 7)] = M.entries[rng.integers(0, M.nnz, size=M.nnz // 7)]   # duplicates
@@ -120,7 +129,8 @@ def run(be, budget, seed0=0, max_cases=None, kinds=None):
                     pc.check_spmv_mv(be, M, int(rng.choice([8, 16, 16, 32, 24, 5])), "N", float(rng.integers(-3, 4)), float(rng.integers(-1, 2)), str(rng.choice(["C", "F"])), str(rng.choice(["C", "F"])),
                                      algo="SPMV_DEFAULT", seed=case, max_val=50.0, nans=bool(rng.random() < 0.3), offset_dtype=odt,
                                      knobs={"mv_kernel": int(rng.choice([0, 0, 2, 3, 5])), "mv_order": int(rng.integers(0, 3)), "mv_strip_min_kb": 50, "mv_strip_l2_kb": int(rng.choice([64, 512])),
-                                            "mv4_wg_per_cu": int(rng.choice([1, 8, 64])), "mv5": int(rng.choice([1, 1, 2, 0])), "mv5_min_fill_pct": int(rng.choice([25, 5, 60]))})
+                                            "mv4_wg_per_cu": int(rng.choice([1, 8, 64])), "mv5": int(rng.choice([1, 1, 2, 0])), "mv5_min_fill_pct": int(rng.choice([25, 5, 60]))},
+                                     **mv_draw(rng))
                 for beta in (0.0, float(rng.integers(-2, 3))):
                     pc.check_spmv(be, M, "N", float(rng.integers(-3, 4)), beta, algo="SPMV_DEFAULT", offset_dtype=odt, max_val=50.0, seed=case, knobs=knobs,
                                   nans=(beta == 0.0), value_dtype=(vdt if vdt == np.float32 and rng.random() < 0.5 else None))

@@ -27,9 +27,78 @@ def fspmv_ok(expected, got, tol):
     return not bad.any(), (float(np.nanmax(err)) if err.size else 0.0)
 
 
+# ------------------------------------------------------------------------------------------- views of padded parents
+# A vector or multivector under test can be a window of a larger parent: every parent cell outside the window holds NaN (X) or a
+# fixed sentinel bit pattern (Y) before the call and must hold the same bits after it.  A read outside the window then reaches a NaN
+# (a NaN mismatch inside the window), a write outside it breaks the sentinel.  The parents are padded on all four sides, so a wrong
+# access lands in memory the test owns.
+SENTINEL_BITS = {np.dtype(np.float64): np.uint64(0x7FF8C0DE5EA1F00D), np.dtype(np.float32): np.uint32(0x7FC5EA1D)}
+_UINT = {np.dtype(np.float64): np.uint64, np.dtype(np.float32): np.uint32}
+VIEWS = ("even_pitch", "odd_start", "tall")
+
+
+def view_spec(kind, nvec, itemsize):
+    """(left, right, top, bottom) padding of the parent around an n x nvec window:
+      even_pitch  a row-major parent's pitch is even and the window's base 16-byte aligned: an odd width reaches the paired
+                  16-byte stores next to the masked last column
+      odd_start   the window begins at an odd column: a row-major base 8 (fp64) / 4 (fp32) bytes off 16-byte alignment, even pitch
+      tall        an odd number of extra rows above and more below: a column-major parent's ld exceeds the window's rows and its
+                  first row is odd"""
+    if kind == "even_pitch":
+        left = 16 // itemsize
+        return (left, 1 if (left + nvec) % 2 else 2, 2, 1)
+    if kind == "odd_start":
+        return (1, 1 if nvec % 2 == 0 else 2, 2, 3)
+    if kind == "tall":
+        return (1, 1, 1, 2)
+    return tuple(kind)
+
+
+def _window_2d(be, M, order, pad, fill_bits=None):
+    """M as the window of a padded parent in `order`; cells outside hold NaN, or the bit pattern fill_bits.  Returns (device window,
+    device parent, host copy of the parent, window slices)"""
+    left, right, top, bottom = pad
+    n, k = M.shape
+    P = np.empty((top + n + bottom, left + k + right), dtype=M.dtype, order=order)
+    if fill_bits is None:
+        P[...] = np.nan
+    else:
+        P.view(_UINT[P.dtype])[...] = fill_bits
+    win = (slice(top, top + n), slice(left, left + k))
+    P[win] = M
+    Pd = _to_dev_2d(be, P)
+    return Pd[win], Pd, P.copy(order="K"), win
+
+
+def _window_1d(be, v, stride, pad=3, fill_bits=None):
+    """v as every stride-th element of a parent padded by `pad` elements at both ends (NaN or fill_bits elsewhere)"""
+    P = np.empty(2 * pad + max(v.size, 1) * stride, dtype=v.dtype)
+    if fill_bits is None:
+        P[...] = np.nan
+    else:
+        P.view(_UINT[P.dtype])[...] = fill_bits
+    win = slice(pad, pad + v.size * stride, stride)
+    P[win] = v
+    Pd = be.from_numpy(P)
+    return Pd[win], Pd, P.copy(), win
+
+
+def assert_outside_unchanged(before, after, win, what):
+    """every cell of the parent outside the window bit-identical to what it held before the call"""
+    outside = np.ones(before.shape, dtype=bool)
+    outside[win] = False
+    u = _UINT[before.dtype]
+    bad = (before.view(u) != after.view(u)) & outside
+    if bad.any():
+        at = np.argwhere(bad)[0]
+        raise AssertionError("sentinel overwritten outside the %s view: %d cells, first at parent %s (window %s): %r" %
+                             (what, int(bad.sum()), tuple(int(i) for i in at), win, after[tuple(at)]))
+
+
 def check_spmv(be, A0, mode="N", alpha=1.0, beta=0.0, algo=None, nans=False, seed=0, offset_dtype=np.int32,
-               max_val=1.0, knobs=None, value_dtype=None, vec_dtype=np.float64, expect=None):
-    """one check_spmv() of the reference test (Test_Sparse_spmv.hpp:168-216)"""
+               max_val=1.0, knobs=None, value_dtype=None, vec_dtype=np.float64, expect=None, x_stride=1, y_stride=1):
+    """one check_spmv() of the reference test (Test_Sparse_spmv.hpp:168-216).  x_stride / y_stride != 1: x and y are strided views
+    of padded parents (NaN around x, a sentinel around y) whose cells outside the view must come back bit-identical"""
     rng = np.random.default_rng(seed)
     trans = mode in "TH"
     nin, nout = (A0.nrows, A0.ncols) if trans else (A0.ncols, A0.nrows)
@@ -38,7 +107,13 @@ def check_spmv(be, A0, mode="N", alpha=1.0, beta=0.0, algo=None, nans=False, see
     if nans:
         y0[::19] = np.nan
     A = dev(be, A0, offset_dtype, value_dtype)
-    xd, yd = be.from_numpy(x), be.from_numpy(y0)
+    views = x_stride != 1 or y_stride != 1
+    if views:
+        xd, xpd, xp0, xwin = _window_1d(be, x, x_stride)
+        yd, ypd, yp0, ywin = _window_1d(be, y0, y_stride, fill_bits=SENTINEL_BITS[np.dtype(vec_dtype)])
+    else:
+        xd, yd = be.from_numpy(x), be.from_numpy(y0)
+    h = None
     if algo is None:
         kk.spmv(mode, alpha, A, xd, beta, yd)
     else:
@@ -49,7 +124,13 @@ def check_spmv(be, A0, mode="N", alpha=1.0, beta=0.0, algo=None, nans=False, see
         kk.spmv(h, mode, alpha, A, xd, beta, yd) if beta == 0.0 else None   # handle reuse
         for k_, v_ in (expect or {}).items():                               # what the analysis must have produced
             assert h.query(k_) == v_, "plan query %s: %r, expected %r" % (k_, h.query(k_), v_)
-    got = be.to_numpy(yd).astype(np.float64)
+    if views:
+        yp = be.to_numpy(ypd)
+        assert_outside_unchanged(yp0, yp, ywin, "y")
+        assert_outside_unchanged(xp0, be.to_numpy(xpd), slice(0, 0), "x")       # x is never written, inside the view or out
+        got = yp[ywin].astype(np.float64)
+    else:
+        got = be.to_numpy(yd).astype(np.float64)
     Ao = A0 if value_dtype is None else oracle.Crs(A0.nrows, A0.ncols, A0.row_map, A0.entries, A0.values.astype(value_dtype))
     if vec_dtype == np.float64:
         exp = oracle.spmv_serial(mode, Ao, alpha, x, beta, y0.copy())
@@ -62,26 +143,34 @@ def check_spmv(be, A0, mode="N", alpha=1.0, beta=0.0, algo=None, nans=False, see
         longest_col = int(np.bincount(A0.entries, minlength=A0.ncols).max()); longest_row = int(np.diff(A0.row_map).max())
         tol *= max(1.0, longest_col / max(longest_row, 1))
     ok, err = fspmv_ok(exp, got, max(tol, 1e-300))
-    assert ok, "spmv mismatch mode=%s alpha=%g beta=%g algo=%s: max err %g > tol %g" % (mode, alpha, beta, algo, err, tol)
-    return h if algo is not None else None
+    assert ok, "spmv mismatch mode=%s alpha=%g beta=%g algo=%s strides=%d,%d: max err %g > tol %g" % (mode, alpha, beta, algo, x_stride, y_stride, err, tol)
+    return h
 
 
 def check_spmv_mv(be, A0, nvec, mode="N", alpha=1.0, beta=0.0, x_order="F", y_order="F", algo=None, seed=0, knobs=None, expect=None,
-                  max_val=1.0, nans=False, offset_dtype=np.int32, value_dtype=None, x_special=None):
-    """x_special: {row: value} written into every column of X after the random fill (Inf / NaN propagation)"""
+                  max_val=1.0, nans=False, offset_dtype=np.int32, value_dtype=None, x_special=None, vec_dtype=np.float64, view=None):
+    """x_special: {row: value} written into every column of X after the random fill (Inf / NaN propagation).
+    vec_dtype: the scalar type of X and Y (fp32 vectors need value_dtype=np.float32).  view: X and Y are windows of padded parents
+    in x_order / y_order (a name of VIEWS or a (left, right, top, bottom) tuple): NaN around X, a sentinel around Y, every cell outside
+    the windows bit-identical after the call"""
     rng = np.random.default_rng(seed)
     trans = mode in "TH"
+    vdt = np.dtype(vec_dtype)
     nin, nout = (A0.nrows, A0.ncols) if trans else (A0.ncols, A0.nrows)
-    X = np.asarray(rng.random((nin, nvec)), order=x_order)
+    X = np.asarray(rng.random((nin, nvec)), order=x_order).astype(vdt, order="K")
     for r_, v_ in (x_special or {}).items():
         X[r_, :] = v_
-    Y0 = np.asarray(rng.random((nout, nvec)), order=y_order)
+    Y0 = np.asarray(rng.random((nout, nvec)), order=y_order).astype(vdt, order="K")
     if nans:
         Y0[::7, :] = np.nan
     if value_dtype is not None:
         A0 = oracle.Crs(A0.nrows, A0.ncols, A0.row_map, A0.entries, A0.values.astype(value_dtype).astype(np.float64))
     A = dev(be, A0, offset_dtype, value_dtype)
-    Xd, Yd = _to_dev_2d(be, X), _to_dev_2d(be, Y0)
+    if view is not None:
+        Xd, Xpd, Xp0, xwin = _window_2d(be, X, x_order, view_spec(view, nvec, vdt.itemsize))
+        Yd, Ypd, Yp0, ywin = _window_2d(be, Y0, y_order, view_spec(view, nvec, vdt.itemsize), fill_bits=SENTINEL_BITS[vdt])
+    else:
+        Xd, Yd = _to_dev_2d(be, X), _to_dev_2d(be, Y0)
     h = None
     if algo is None:
         kk.spmv(mode, alpha, A, Xd, beta, Yd)
@@ -94,18 +183,27 @@ def check_spmv_mv(be, A0, nvec, mode="N", alpha=1.0, beta=0.0, x_order="F", y_or
             kk.spmv(h, mode, alpha, A, Xd, beta, Yd)                            # handle reuse
         for k_, v_ in (expect or {}).items():
             assert h.query(k_) == v_, "plan query %s: %r, expected %r" % (k_, h.query(k_), v_)
-    got = _to_host_2d(be, Yd)
-    exp = oracle.spmv_mv_serial(mode, A0, alpha, X, beta, Y0.copy(order="K"))
+    if view is not None:
+        Yp = _to_host_2d(be, Ypd)
+        assert_outside_unchanged(Yp0, Yp, ywin, "Y")
+        assert_outside_unchanged(Xp0, _to_host_2d(be, Xpd), (slice(0, 0), slice(0, 0)), "X")
+        got = Yp[ywin].astype(np.float64)
+    else:
+        got = _to_host_2d(be, Yd).astype(np.float64)
+    # the expected result in float64 from the (fp32-rounded) inputs; fp32 vectors scale the reference's bound by EPS_F / eps(f64)
+    exp = oracle.spmv_mv_serial(mode, A0, alpha, X.astype(np.float64, order="K"), beta, Y0.astype(np.float64, order="K"))
     tol = oracle.spmv_max_error(A0, alpha, beta, max_val=max_val)
+    if vdt == np.float32:
+        tol *= EPS_F / np.finfo(np.float64).eps
     if trans and A0.nnz:      # a transposed product accumulates per COLUMN: scale the reference's bound by the longest column instead (as check_spmv does)
         longest_col = int(np.bincount(A0.entries, minlength=A0.ncols).max()); longest_row = int(np.diff(A0.row_map).max())
         tol *= max(1.0, longest_col / max(longest_row, 1))
-    assert not (np.isnan(exp) ^ np.isnan(got)).any(), "spmv_mv NaN mismatch nvec=%d" % nvec
+    assert not (np.isnan(exp) ^ np.isnan(got)).any(), "spmv_mv NaN mismatch nvec=%d view=%s" % (nvec, view)
     inf = np.isinf(exp)
     assert np.array_equal(inf, np.isinf(got)) and np.array_equal(exp[inf], got[inf]), "spmv_mv Inf mismatch nvec=%d" % nvec
     exp = np.where(inf, 0.0, exp); got = np.where(inf, 0.0, got)
     err = np.nanmax(np.abs(exp - got)) if got.size else 0.0
-    assert err <= max(tol, 1e-300), "spmv_mv mismatch nvec=%d mode=%s orders=%s%s: %g > %g" % (nvec, mode, x_order, y_order, err, tol)
+    assert err <= max(tol, 1e-300), "spmv_mv mismatch nvec=%d mode=%s orders=%s%s view=%s %s: %g > %g" % (nvec, mode, x_order, y_order, view, vdt, err, tol)
     return h
 
 
@@ -1217,3 +1315,223 @@ def mv3_cases():
         ent = np.insert(ent, rm[r + 1], extra); val = np.insert(val, rm[r + 1], rng.random(2500)); rm[r + 1:] += 2500
     out.append(("5pt+long-rows", oracle.Crs(A0.nrows, A0.ncols, rm, ent, val), True))
     return out
+
+
+# ------------------------------------------------------------------------------------------- rank 2: route x type x layout
+# (value type, vector type) pairs of the C ABI; a value type of None is fp64
+TYPE_PAIRS = ((None, np.float64), (np.float32, np.float64), (np.float32, np.float32))
+# (x order, y order, view): contiguous in the four layout pairs, then windows of padded parents (section "views" above)
+LAYOUTS = (("C", "C", None), ("F", "F", None), ("C", "F", None), ("F", "C", None), ("C", "C", "even_pitch"), ("C", "C", "odd_start"),
+           ("F", "F", "tall"), ("C", "F", "even_pitch"), ("F", "C", "odd_start"), ("C", "F", "tall"), ("F", "C", "even_pitch"))
+# (alpha, beta) of the route cells: beta = 0 runs over NaN in Y (alpha = 0 never reaches a kernel: its own cells scale Y)
+ALPHA_BETA = ((1.5, 0.0), (-1.0, 0.5), (1.5, -1.0), (-1.0, 0.0))
+
+
+def _tp_name(vt, yt):
+    return "%s/%s" % ("f32" if vt is not None else "f64", "f32" if yt == np.float32 else "f64")
+
+
+def _mv2_window(A0, nvec):
+    """staging window spmv_mv2_kernel compiles for this width and matrix (kk_spmv_mv.hip, KK_MV2)"""
+    L = 4 if nvec >= 12 else (2 if nvec >= 3 else 1)
+    need = int(1.15 * (64 // L) * A0.nnz / A0.nrows) + 4
+    return L, (256 if need <= 256 else (512 if need <= 512 else 1024))
+
+
+def check_mv_route_matrix(be, light=False, log=None):
+    """every rank-2 route x the three (value, vector) type pairs x int32 / int64 offsets x layouts (contiguous C / F, the four pairs,
+    windows of padded parents), compared with the float64 oracle, outside cells guarded, the route confirmed by plan queries.
+    log: a list the cells are appended to (route, types, offsets, width, layout, what confirmed it).  Returns the set of
+    (offset bits, value type, mv4_stencil) that launched the plane-marching kernel."""
+    log = [] if log is None else log
+    offs = (np.int32, np.int64)
+    cyc = [0]
+
+    def layout():
+        cyc[0] += 1
+        return LAYOUTS[cyc[0] % len(LAYOUTS)]
+
+    def ab():
+        return ALPHA_BETA[cyc[0] % len(ALPHA_BETA)]
+
+    def run(route, A0, nvec, vt, yt, off, algo, knobs=None, mode="N", lay=None, max_val=1.0, expect=None, seed=0, ab_=None):
+        xo, yo, view = lay or layout()
+        alpha, beta = ab_ or ab()
+        h = check_spmv_mv(be, A0, nvec, mode, alpha, beta, xo, yo, algo=algo, knobs=knobs, max_val=max_val, nans=(beta == 0.0),
+                          offset_dtype=off, value_dtype=vt, vec_dtype=yt, view=view, seed=seed + nvec)
+        got = {}
+        for k_, want in (expect or {}).items():
+            got[k_] = h.query(k_)
+            ok = want(got[k_]) if callable(want) else got[k_] == want
+            assert ok, "%s %s off=%s nvec=%d %s%s view=%s: plan query %s = %r" % (route, _tp_name(vt, yt), np.dtype(off).name, nvec, xo, yo, view,
+                                                                                   k_, got[k_])
+        log.append((route, _tp_name(vt, yt), np.dtype(off).name, nvec, "%s%s%s" % (xo, yo, "/%s" % (view,) if view else ""), alpha, beta,
+                    ", ".join("%s=%d" % kv for kv in got.items()) or "no handle"))
+        return h
+
+    f64v = lambda yt: yt == np.float64
+    tps = TYPE_PAIRS
+    # 1. the handle-less generic kernel: X that is not 16-byte row-major (column-major, odd pitch, odd start); SW 2 / 4 / 8 / 16
+    A0 = oracle.random_crs(700 if light else 1500, 650 if light else 1400, 9, variance=4, seed=41)
+    for nvec in ((2, 3, 6, 12, 17) if not light else (2, 3, 6, 12)):
+        odd_pitch = (2, 1, 2, 1) if nvec % 2 == 0 else (2, 2, 2, 1)
+        lays = (("F", "C", None), ("C", "C", "odd_start"), ("C", "F", odd_pitch), ("F", "F", "tall"))
+        for ti, (vt, yt) in enumerate(tps):
+            for oi, off in enumerate(offs):
+                run("generic (no handle)", A0, nvec, vt, yt, off, None, lay=lays[(ti * 2 + oi + nvec) % 4])
+    # 2. spmv_mv2_kernel, X row-major (direct) or packed, every lane shape (widths) x staging window (average row length) x NT
+    avgs = {1: (3, 6, 12), 2: (5, 10, 20), 4: (9, 20, 40)}
+    mats = {a: oracle.random_crs(600 if light else 1200, 1100, a, variance=0, seed=50 + a) for L in avgs for a in avgs[L]}
+    seen = set()
+    for nvec in ((2, 3, 5, 6, 12, 16, 21, 32) if not light else (2, 3, 6, 12)):
+        L = 4 if nvec >= 12 else (2 if nvec >= 3 else 1)
+        for wi, a in enumerate(avgs[L]):
+            Lw, win = _mv2_window(mats[a], nvec)
+            for nt in ((0, 1) if not light else (wi % 2,)):
+                for ti, (vt, yt) in enumerate(tps):
+                    off = offs[(ti + wi + nt) % 2]
+                    direct = (ti + nt) % 2 == 0
+                    lay = (("C", "C", None) if nvec % 2 == 0 else ("C", "C", "even_pitch")) if direct else layout()
+                    if not direct and lay[0] == "C" and lay[2] in (None, "even_pitch") and nvec % 2 == 0:
+                        lay = ("F",) + lay[1:]
+                    algo = "SPMV_DEFAULT" if (nvec + wi + ti) % 3 else None
+                    if algo is None and not direct:
+                        algo = "SPMV_DEFAULT"
+                    run("mv2 L%d win%d nt%d %s" % (Lw, win, nt, "direct" if direct else "packed"), mats[a], nvec, vt, yt, off, algo,
+                        knobs={"mv_kernel": 2, "mv_nt": nt}, lay=lay,
+                        expect=None if algo is None else {"mv4_workgroups": 0, "mv5_tiles": 0, "mv6_chunks": 0, "mv_tiles": 0, "mv_long_rows": 0})
+                    seen.add((Lw, win, nt))
+    want = {(L, w, nt) for L in (1, 2, 4) for w in (256, 512, 1024) for nt in (0, 1)}
+    assert light or seen == want, sorted(want - seen)
+    # 3. the long-row kernel (rows above the threshold, a workgroup each) after the gather kernel
+    H = hub_matrix(1500, 5000, 6, {5: 3000, 17: 1500, 700: 1025, 1499: 2000, 40: 1024}, seed=3)
+    for ni, nvec in enumerate((2, 5, 16, 17, 33) if not light else (5, 17)):
+        for ti, (vt, yt) in enumerate(tps):
+            run("long rows", H, nvec, vt, yt, offs[(ni + ti) % 2], "SPMV_DEFAULT", knobs={"mv6": 0, "mv_long_T": 1024}, max_val=50.0,
+                expect={"mv_long_rows": 4, "mv6_chunks": 0})
+    # 4. mv3: LDS-staged X tiles (fp64 vectors only: fp32 vectors fall back to the gather kernel with the tile queries at 0)
+    M3 = mv3_cases()[0][1]
+    for nvec in ((8, 16) if not light else (8,)):
+        for ti, (vt, yt) in enumerate(tps):
+            for off in (offs if not light else offs[ti % 2:ti % 2 + 1]):
+                run("mv3", M3, nvec, vt, yt, off, "SPMV_DEFAULT", knobs={"mv_kernel": 3}, max_val=32.0,
+                    expect={"mv_staged_tiles": (lambda v: v > 0) if f64v(yt) else 0, "mv_tiles": (lambda v: v > 0) if f64v(yt) else 0})
+    # 5. mv4 on each of its stencil code objects (27-pt, 7-pt, 19-pt = 9 groups, 11-pt = 5 groups), full and partial blocks
+    launched = set()
+    cases = mv4_cases()
+    m4 = [cases[i][1] for i in (0, 1, 4, 5)]
+    for mi, M in enumerate(m4):
+        for ti, (vt, yt) in enumerate(tps):
+            for oi, off in enumerate(offs):
+                for nvec in ((5, 16, 21) if not light else ((5,) if (mi + ti + oi) % 2 else (16,))):
+                    lay = ("C", "C", "even_pitch") if nvec % 2 else None        # odd widths: the paired stores beside the masked column
+                    h = run("mv4", M, nvec, vt, yt, off, "SPMV_DEFAULT", lay=lay, max_val=32.0,
+                            expect={"mv4_workgroups": (lambda v: v > 0) if f64v(yt) else 0})
+                    if f64v(yt):
+                        launched.add((np.dtype(off).itemsize * 8, "f32" if vt is not None else "f64", h.query("mv4_stencil")))
+    # 6. mv5 (matrix cores): widths 1 - 5 (the nc = 2 pass), 16, 17, 37; a described block-diagonal matrix, gather rows on another
+    B, B2 = mv5_cases()[0][1], mv5_cases()[1][1]
+    for ni, nvec in enumerate((1, 2, 3, 4, 5, 16, 17, 37) if not light else (1, 3, 17)):
+        for ti, (vt, yt) in enumerate(tps):
+            M = B if (ni + ti) % 2 == 0 else B2
+            lay = ("C", "C", ("even_pitch", "odd_start")[ti % 2]) if nvec == 1 else None   # width 1 reaches rank 2 only as a strided view
+            run("mv5", M, nvec, vt, yt, offs[(ni + ti) % 2], "SPMV_DEFAULT", lay=lay, max_val=1.5,
+                expect={"mv5_tiles": (lambda v: v > 0) if f64v(yt) else 0})
+    # 7. mv6 (nonzero split), forced
+    name, M6 = mv6_cases()[4 if light else 0]
+    for ni, nvec in enumerate((1, 2, 5, 16, 33) if not light else (1, 5)):
+        for ti, (vt, yt) in enumerate(tps):
+            lay = ("C", "C", "even_pitch") if nvec % 2 else None
+            run("mv6", M6, nvec, vt, yt, offs[(ni + ti) % 2], "SPMV_DEFAULT", knobs={"mv6": 2}, lay=lay, max_val=50.0,
+                expect={"mv6_chunks": -(-M6.nnz // 128) if f64v(yt) else 0})
+    # 8. modes T / H: the cached transpose (mode-N dispatch on it) and the atomic kernel (explicit_transpose 0, and no handle)
+    T0 = oracle.random_crs(300 if light else 2000, 250 if light else 1600, 9, variance=4, seed=43)
+    for ni, nvec in enumerate((1, 3, 16, 17) if not light else (1, 3)):
+        for ti, (vt, yt) in enumerate(tps):
+            for mi, mode in enumerate("TH"):
+                lay = ("C", "C", "odd_start") if nvec == 1 else None
+                off = offs[(ni + ti + mi) % 2]
+                run("%s cached transpose" % mode, T0, nvec, vt, yt, off, "SPMV_DEFAULT", mode=mode, lay=lay,
+                    knobs={"explicit_transpose_min_knnz": 0}, expect={"transpose_cached": 1})
+                run("%s atomics" % mode, T0, nvec, vt, yt, off, "SPMV_DEFAULT", mode=mode, lay=lay,
+                    knobs={"explicit_transpose": 0}, expect={"transpose_cached": 0})
+                if mi == 0:
+                    run("T atomics (no handle)", T0, nvec, vt, yt, off, None, mode=mode, lay=lay)
+    # 9. alpha = 0: Y scaled by beta (0 over NaN), no kernel of the product; every type pair and layout
+    for li, lay in enumerate(LAYOUTS):
+        for ti, (vt, yt) in enumerate(tps):
+            for beta in (0.0, 0.5):
+                run("alpha 0 (scale Y)", A0, (3, 16, 1)[(li + ti) % 3] if lay[2] else (3, 16)[(li + ti) % 2], vt, yt, offs[(li + ti) % 2],
+                    "SPMV_DEFAULT" if (li + ti) % 2 else None, lay=lay, ab_=(0.0, beta))
+    return launched
+
+
+def check_strided_rank1(be, light=False):
+    """rank-1 x / y as strided views (every k-th element of a padded parent): modes N and T, with and without a handle, on a random
+    matrix, a block-diagonal matrix (the matrix-core rank-2 kernel at width 1) and a lattice; a strided x / y for spmv_struct"""
+    import pytest
+    mats = [("random", oracle.random_crs(700, 640, 9, variance=4, seed=61), 1.0),
+            ("block diagonal", block_diagonal(20 if light else 40, 32, 1), 1.5),
+            ("27-pt lattice", oracle.laplace3d("FE", 12, 10, 9) if light else mv4_cases()[0][1], 32.0)]
+    strides = ((2, 1), (1, 3), (2, 2), (5, 4))
+    for mi, (name, A0, mv) in enumerate(mats):
+        for si, (xs, ys) in enumerate(strides):
+            for mode in "NT":
+                for algo in (None, "SPMV_DEFAULT"):
+                    vt, yt = TYPE_PAIRS[(mi + si) % 3]
+                    alpha, beta = (0.0, 0.5) if si == 3 and mode == "N" and algo is None else ALPHA_BETA[(si + mi + (mode == "T")) % len(ALPHA_BETA)]
+                    h = check_spmv(be, A0, mode, alpha, beta, algo, nans=(beta == 0.0), max_val=mv, x_stride=xs, y_stride=ys,
+                                   value_dtype=vt, vec_dtype=yt, seed=si)
+                    if h is not None and name == "block diagonal" and mode == "N" and yt == np.float64 and alpha != 0.0:
+                        assert h.query("mv5_tiles") > 0, (name, xs, ys)
+    # spmv_struct: a strided x (and y) takes the unstructured path on the leading numCols / numRows elements of longer vectors
+    for dims, stt in (((25, 21), 1), ((10, 12, 9), 2)):
+        A0 = struct_matrix(dims, stt)
+        for mode in "NT":
+            for xs, ys, extra in ((2, 1, 0), (3, 2, 5), (1, 2, 3)):
+                rng = np.random.default_rng(xs + 7 * ys)
+                nin, nout = (A0.nrows, A0.ncols) if mode == "T" else (A0.ncols, A0.nrows)
+                x = rng.random(nin + extra); y0 = rng.random(nout + extra)
+                xd, xpd, xp0, xwin = _window_1d(be, x, xs)
+                yd, ypd, yp0, ywin = _window_1d(be, y0, ys, fill_bits=SENTINEL_BITS[np.dtype(np.float64)])
+                kk.spmv_struct(mode, stt, dims, 1.5, dev(be, A0), xd, 0.5, yd)
+                yp = be.to_numpy(ypd)
+                assert_outside_unchanged(yp0, yp, ywin, "y")
+                assert_outside_unchanged(xp0, be.to_numpy(xpd), slice(0, 0), "x")
+                exp = y0.copy()
+                exp[:nout] = oracle.spmv_serial(mode, A0, 1.5, x[:nin].copy(), 0.5, y0[:nout].copy())
+                ok, err = fspmv_ok(exp, yp[ywin], oracle.spmv_max_error(A0, 1.5, 0.5, max_val=32.0))
+                assert ok, ("spmv_struct strided", dims, mode, xs, ys, err)
+    # numpy / torch can make views the C ABI cannot take (reversed, broadcast): refused before any work, y untouched
+    A0 = mats[0][1]
+    A = dev(be, A0)
+    y0 = np.full(2 * A0.nrows, 3.0)
+    y, one = be.from_numpy(y0), be.from_numpy(np.ones(A0.ncols))
+    if be.name == "emu":
+        as_strided = np.lib.stride_tricks.as_strided
+        bad = ((one[::-1], y[::2]), (as_strided(one, (A0.ncols,), (0,)), y[::2]), (one, as_strided(y, (A0.nrows,), (0,))))
+    else:
+        bad = ((one[:1].expand(A0.ncols), y[::2]), (one, y[:1].expand(A0.nrows)))
+    for xb, yb in bad:
+        with pytest.raises(RuntimeError, match="positive strides only"):
+            kk.spmv("N", 1.0, A, xb, 0.0, yb)
+    assert np.array_equal(be.to_numpy(y), y0)
+
+
+def check_unsupported_pair_leaves_y(be):
+    """an fp64 matrix with fp32 vectors is refused whatever alpha and the matrix are, before Y is touched"""
+    import pytest
+    for A0 in (oracle.random_crs(50, 40, 4, seed=1), oracle.random_crs(50, 40, 0, seed=1)):
+        A = dev(be, A0)
+        for alpha in (0.0, 1.0):
+            y0 = np.linspace(1.0, 2.0, 50).astype(np.float32)
+            y = be.from_numpy(y0)
+            with pytest.raises(kk.KkamdError) as ei:
+                kk.spmv("N", alpha, A, be.from_numpy(np.ones(40, np.float32)), 0.5, y)
+            assert ei.value.status == kk._capi.ERR_UNSUPPORTED
+            Y0 = np.ones((50, 3), np.float32)
+            Y = _to_dev_2d(be, Y0)
+            with pytest.raises(kk.KkamdError) as ei:
+                kk.spmv("N", alpha, A, _to_dev_2d(be, np.ones((40, 3), np.float32)), 0.5, Y)
+            assert ei.value.status == kk._capi.ERR_UNSUPPORTED
+            assert np.array_equal(be.to_numpy(y), y0) and np.array_equal(_to_host_2d(be, Y), Y0)

@@ -37,6 +37,15 @@ def test_argument_validation_without_device_work():
     d.d_row_map = 8  # never dereferenced: mode is rejected first
     assert lib.kkamd_spmv(None, C.byref(d), b"Q", 1.0, None, 0.0, None, 1, None) == kk._capi.ERR_INVALID_ARG
     assert b"Invalid transpose mode" in lib.kkamd_last_error()
+    # an fp64 matrix with fp32 vectors is refused before the alpha == 0 / empty-matrix shortcut (which would scale y on the device)
+    for nnz in (0, 5):
+        d.nnz, d.d_entries, d.d_values = nnz, 8, 8
+        for alpha in (0.0, 1.0):
+            assert lib.kkamd_spmv(None, C.byref(d), b"N", alpha, None, 0.5, None, kk._capi.F32, None) == kk._capi.ERR_UNSUPPORTED
+            assert b"type pair" in lib.kkamd_last_error()
+            assert lib.kkamd_spmv_mv(None, C.byref(d), b"N", alpha, None, 1, 4, 0.5, None, 1, 4, 2, kk._capi.F32, None) == kk._capi.ERR_UNSUPPORTED
+            assert b"type pair" in lib.kkamd_last_error()
+    d.nnz, d.d_entries, d.d_values = 0, None, None
     p = C.c_void_p()
     assert lib.kkamd_spmv_plan_create(C.byref(p), C.byref(d), 99, None) == kk._capi.ERR_INVALID_ARG
     assert lib.kkamd_spgemm_numeric(None, 1, 1, 1, None, None, None, None, None, None, None, None, None, 0, 1, None) == kk._capi.ERR_STATE

@@ -609,3 +609,20 @@ def test_column_slab_follows_value_changes(be):
     v[[0, len(v) - 1]] = v[[len(v) - 1, 0]]               # two values swapped (the plain sum of the bits does not move)
     A.values[:] = be.from_numpy(v)
     run_and_check(v)
+
+
+def test_mv_route_type_layout_matrix(be):
+    # rank 2: every route (generic, wave-private gather in every lane shape / staging window / NT, long rows, LDS-staged, plane marching
+    # on its four stencil code objects, matrix cores, nonzero split, modes T / H cached and atomic, alpha = 0) x the three (value,
+    # vector) type pairs x int32 / int64 offsets x contiguous C / F pairs and windows of padded parents, outside cells guarded
+    launched = pc.check_mv_route_matrix(be, light=True)
+    assert len(launched) == 16, sorted(launched)
+
+
+def test_strided_rank1_vectors(be):
+    # rank-1 x / y that are strided views (a column of a row-major multivector): the rank-2 path at width 1, nothing outside written
+    pc.check_strided_rank1(be, light=True)
+
+
+def test_unsupported_type_pair_whatever_alpha(be):
+    pc.check_unsupported_pair_leaves_y(be)

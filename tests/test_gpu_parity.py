@@ -318,6 +318,32 @@ def test_mv4_widths_beyond_one_block(be):
     pc.check_spmv_mv(be, A0, 24, "T", 2.0, 0.5, "F", "F", algo="SPMV_DEFAULT", max_val=32.0, knobs={"explicit_transpose_min_knnz": 0})
 
 
+def test_mv_route_type_layout_matrix(be):
+    # rank 2: every route x (value, vector) type pair x int32 / int64 offsets x layouts (contiguous C / F in the four pairs, windows of
+    # padded parents: even pitch with an aligned base, odd start, column-major with ld > rows), outside cells guarded, routes confirmed
+    # by plan queries; the plane-marching kernel launched from all 16 of its code objects (offsets x value type x stencil)
+    log = []
+    launched = pc.check_mv_route_matrix(be, light=False, log=log)
+    cells = {}
+    for route, types, off, nvec, lay, alpha, beta, conf in log:
+        cells.setdefault((route, types), []).append("%s w%d %s %s" % (off, nvec, lay, conf))
+    for (route, types), v in sorted(cells.items()):
+        print("cell %-34s %s  %d runs: %s" % (route, types, len(v), "; ".join(sorted(set(v)))))
+    print("mv4 code objects launched:", sorted(launched))
+    want = {(ob, vt, st) for ob in (32, 64) for vt in ("f32", "f64") for st in (27, 7, 11, 19)}
+    assert launched == want, sorted(want - launched)
+
+
+def test_strided_rank1_vectors(be):
+    # rank-1 x / y that are strided views: the rank-2 path at width 1 (the matrix-core kernel on a block-diagonal matrix), spmv_struct
+    # on longer strided vectors, reversed / broadcast views refused
+    pc.check_strided_rank1(be)
+
+
+def test_unsupported_type_pair_leaves_y(be):
+    pc.check_unsupported_pair_leaves_y(be)
+
+
 def test_mv4_duplicate_entries(be):
     # a lattice row that stores one column twice must never become the plane-marching pattern, and a row
     # with a duplicate must go to the gather rows (the reference sums duplicates); rank 2 and the rank-1 marching kernel
