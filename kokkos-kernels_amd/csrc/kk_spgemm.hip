@@ -32,7 +32,11 @@
 //   4. every numeric kernel leaves its rows column-sorted, so the reference's extra sort pass over C
 //      (numeric_spec.hpp:138-140) disappears.
 // Symbolic results are exact (bit-identical row_map / entries to the SPGEMM_DEBUG oracle after its
-// sort); numeric sums are order-dependent (atomics) and compared at 1e-6 relative.
+// sort); numeric sums are order-dependent (atomics).  The suite compares them three ways: with the reference's own
+// comparator (|a-b| / (|a|+|b|) <= 1e-7 for fp64, 3.7e-3 for fp32: tests/parity_cases.py check_spgemm), bit for bit on
+// signed inputs whose every partial sum is exactly representable (check_spgemm_exact: signs, cancellation to a stored
+// zero, Inf / NaN / explicit zeros, numeric reuse, through every value kernel), and within the textbook bound
+// (n + 1) u sum|a*b| per entry on signed real values against a long-double sum (its mode "bound").
 #include "kk_common.h"
 #include "kk_scan.h"
 #include <climits>
@@ -4529,6 +4533,26 @@ static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const voi
   hipError_t e2 = hipStreamSynchronize(st);   // the reference's numeric phase fences too (impl_kkmem.hpp:1440,1467)
   if (e != hipSuccess || e2 != hipSuccess) { h->entries_valid = false; return fail(KKAMD_ERR_HIP, "spgemm numeric failed: %s", hipGetErrorString(e != hipSuccess ? e : e2)); }
   h->entries_valid = true; h->entC_ptr = entC; h->rmC_ptr = rmC_;
+  if (h->verbose) {
+    // which VALUE kernel took how many rows (the line above counts the bins; a bin's kernel depends on B being sorted and on the knobs).
+    // The exact-value tests read this line to prove that their cases reached every kernel.
+    const bool flat = g_spgemm.val_kernel == 2 && h->dense_lds, mid = flat && h->hub_from_mid && !g_spgemm.val_hub_flat;
+    const int64_t n4 = nb(4), n_blk = n4 ? h->n_dense_block : 0, n_lds = n4 ? h->n_dense_lds : 0, n_hubl = n4 ? h->n_dense_hub_lds : 0;
+    const int64_t n_rest = n4 - n_blk - n_lds - n_hubl;
+    const int64_t n_quad = nb(1) ? (h->n_wave_quad < nb(1) ? h->n_wave_quad : nb(1)) : 0;
+    const int64_t n_tiny = flat ? (h->n_dense_tiny < n_lds ? h->n_dense_tiny : n_lds) : 0;
+    const int64_t n_small = flat ? (h->n_dense_small < n_lds - n_tiny ? h->n_dense_small : n_lds - n_tiny) : 0;
+    const bool items = n_blk && g_spgemm.items && h->items_ready && h->items_cap == g_spgemm.item_cap && h->idx_nblk <= 4096 && h->idx_wshift >= 5;
+    const int64_t n_hub_rows = g_spgemm.val_hub_flat && flat ? 0 : (mid ? n_rest : n_hubl);
+    // quad / wave: wave bin, four rows per wave / one; items_rank, items_direct: ITEMS of the column-block rows, position- / column-indexed; blocks_wg: those rows
+    // with one workgroup per (row, block); win128 .. win1024: the flat value windows by work-items; hub_multi: hub rows in several passes; hbm: k-wide accumulator
+    KK_VERBOSE("\tkkamd spgemm numeric (%s): rows per value kernel -- quad=%lld wave=%lld block_small=%lld block_large=%lld blocks=%lld items_rank=%lld "
+               "items_direct=%lld blocks_wg=%lld win128=%lld win256=%lld win512=%lld win1024=%lld hub=%lld hub_multi=%lld hbm=%lld\n",
+               h->algorithm == 1 ? "SPGEMM_KK_DENSE" : "SPGEMM_KK", (long long)n_quad, (long long)(nb(1) - n_quad), (long long)nb(2), (long long)nb(3),
+               (long long)n_blk, (long long)(items ? h->n_items_rank : 0), (long long)(items ? h->n_items_direct : 0), (long long)(n_blk && !items ? n_blk : 0),
+               (long long)n_tiny, (long long)n_small, (long long)(flat ? n_lds - n_tiny - n_small : n_lds), (long long)(mid ? n_hubl : 0),
+               (long long)n_hub_rows, (long long)(mid && h->d_hub_items ? h->n_hub_multi : 0), (long long)(flat ? (mid || g_spgemm.val_hub_flat ? 0 : n_rest) : n_rest));
+  }
   if (h->d_bm_store || h->unit_mode) { const int64_t used = h->bitmaps_used; free_bitmap_store(h); h->bitmaps_used = used; }    // entries(C) are written: the bitmaps (GBs) are not needed again
   return KKAMD_OK;
 }

@@ -6,6 +6,9 @@ seeded inputs, with the reference's own comparators and tolerances:
   SpGEMM row_map and entries IDENTICAL, values |a-b|/(|a|+|b|) <= 1e-7
          (sparse/unit_test/Test_Sparse_Utils.hpp:39-127)
 """
+import math
+import re
+
 import numpy as np
 
 import kk_loader
@@ -583,17 +586,14 @@ def check_spgemm(be, A0, B0, offset_dtype=np.int32, reuse=True, value_dtype=np.f
     return got
 
 
-def check_spgemm_kept_structure(be):
-    """The symbolic phase keeps, for the first numeric call, the bitmaps of its densest rows (>= k/32 entries) and the ENTRY LISTS of the
-    other dense rows (round 4; lists above 6144 entries leave LDS in several rounds): structure identical to the oracle's, both sources
-    used, numeric reuse keeps the entries, and with the lists switched off the same C comes out"""
+def kept_structure_operands():
+    """(A, B, Ad, Bd) of check_spgemm_kept_structure: hub lists of B over 400000 columns under short rows of A, and rows of C that are
+    30 .. 100 % dense (kept bitmaps whose 64-word steps hold more than a wave's 1024 staging slots: halves, quarters)"""
     import fuzz_cases as fz
     rng = np.random.default_rng(5)
     n, k = 60, 400000
     B = fz.hubby(rng, n, k, 3000, 0, 3000)            # rows of B: 0 .. 6000 entries
     A = fz.hubby(rng, 10, n, 3, 2, 20)                # rows of A: 0 .. 6 entries, two of about 20
-    gold = oracle.spgemm(A, B)
-    # rows of C that are 30 .. 100 % dense (kept bitmaps whose 64-word steps hold more than a wave's 1024 staging slots: halves, quarters)
     kd = 8192
     lens = rng.integers(1500, 6000, size=30)
     rmd = np.zeros(31, dtype=np.int64); np.cumsum(lens, out=rmd[1:])
@@ -601,6 +601,15 @@ def check_spgemm_kept_structure(be):
     rows_d = [np.sort(rng.choice(30, size=c, replace=False)) for c in (1, 2, 3, 6, 12, 30)]
     armd = np.zeros(len(rows_d) + 1, dtype=np.int64); np.cumsum([len(r) for r in rows_d], out=armd[1:])
     Ad0 = oracle.Crs(len(rows_d), 30, armd, np.concatenate(rows_d).astype(np.int32), 1 + 49 * rng.random(armd[-1]))
+    return A, B, Ad0, Bd0
+
+
+def check_spgemm_kept_structure(be):
+    """The symbolic phase keeps, for the first numeric call, the bitmaps of its densest rows (>= k/32 entries) and the ENTRY LISTS of the
+    other dense rows (round 4; lists above 6144 entries leave LDS in several rounds): structure identical to the oracle's, both sources
+    used, numeric reuse keeps the entries, and with the lists switched off the same C comes out"""
+    A, B, Ad0, Bd0 = kept_structure_operands()
+    gold = oracle.spgemm(A, B)
     got_d = check_spgemm(be, Ad0, Bd0)
     assert np.diff(got_d.row_map).max() > 8000 and np.diff(got_d.row_map).min() >= 1500
     kh = kk.KokkosKernelsHandle(be); kh.create_spgemm_handle("SPGEMM_KK")
@@ -629,16 +638,12 @@ def check_spgemm_kept_structure(be):
             kk._capi.check(be.lib, be.lib.kkamd_set_default(b"spgemm_keep_lists", 1))
 
 
-def check_spgemm_units(be, light=False):
-    """Round 6: the symbolic phase counts its dense class by UNITS (row of C, window of 2^unit_bits columns; an index of B at window
-    granularity cuts every list).  Windows of 64 .. 2^18 columns over products whose rows are sparse, dense, a single list, hundreds of
-    lists (several chunks of 256), lists shorter than a quad, empty pieces in most windows; 32- and 64-bit offsets; with the bitmaps,
-    the lists or both switched off; against the one-workgroup-per-row kernel (spgemm_sym_units 0).  Structure identical to the oracle's
-    every time (check_spgemm), and the queries say the units were used."""
+def units_operands():
+    """the three products of check_spgemm_units as [(A, B, name)], and the generator that drew them (the check goes on drawing from it):
+    (a) hub lists next to short ones, k not a multiple of any window; (b) dense rows; (c) an A row of 700 lists (three chunks), B rows of
+    0 .. 30 entries"""
     import fuzz_cases as fz
     rng = np.random.default_rng(61)
-    setd = lambda key, v: kk._capi.check(be.lib, be.lib.kkamd_set_default(key, v))
-    # (a) hub lists next to short ones, k not a multiple of any window; (b) dense rows; (c) an A row of 700 lists (three chunks), B rows of 0 .. 30 entries
     n, k = 60, 100003
     B = fz.hubby(rng, n, k, 2500, 0, 2500)
     A = fz.hubby(rng, 10, n, 3, 2, 20)
@@ -652,7 +657,18 @@ def check_spgemm_units(be, light=False):
     Bs = randomized(oracle.random_crs(900, 30000, 14, variance=14, seed=23, sorted_rows=True))
     cols = np.sort(rng.choice(900, size=700, replace=False)).astype(np.int32)
     As = oracle.Crs(3, 900, np.array([0, 700, 703, 1100]), np.concatenate([cols, [1, 5, 9], np.sort(rng.choice(900, size=397, replace=False))]).astype(np.int32), 1 + 49 * rng.random(1100))
-    cases = [(A, B, "hubs"), (Ad, Bd, "dense"), (As, Bs, "many short lists")]
+    return [(A, B, "hubs"), (Ad, Bd, "dense"), (As, Bs, "many short lists")], rng
+
+
+def check_spgemm_units(be, light=False):
+    """Round 6: the symbolic phase counts its dense class by UNITS (row of C, window of 2^unit_bits columns; an index of B at window
+    granularity cuts every list).  Windows of 64 .. 2^18 columns over products whose rows are sparse, dense, a single list, hundreds of
+    lists (several chunks of 256), lists shorter than a quad, empty pieces in most windows; 32- and 64-bit offsets; with the bitmaps,
+    the lists or both switched off; against the one-workgroup-per-row kernel (spgemm_sym_units 0).  Structure identical to the oracle's
+    every time (check_spgemm), and the queries say the units were used."""
+    setd = lambda key, v: kk._capi.check(be.lib, be.lib.kkamd_set_default(key, v))
+    cases, rng = units_operands()
+    (A, B, _), (Ad, Bd, _), _ = cases
     try:
         for bits in ((6, 12, 18) if light else (6, 9, 12, 15, 18)):
             setd(b"spgemm_unit_bits", bits)
@@ -800,12 +816,8 @@ def check_spgemm_galerkin(be):
     check_spgemm(be, R, AP, value_dtype=np.float32)
 
 
-def check_spgemm_block_kernel(be):
-    """Column-block value kernel (round 5, `spgemm_block`): rows of C that are dense, or have more lists than the flat kernel's shapes
-    hold, accumulate per (row, column block) in a direct-indexed LDS accumulator, with the pieces of every list taken from an index of
-    B.  Cases: k not a multiple of the block width, blocks with no entry of a row, an A row of 2500 lists (three chunks of lists into
-    one accumulator), a row that is 100 % dense, lists that end B's arrays (guarded 16-byte loads), empty B rows inside an A row,
-    numeric reuse (the index of B is kept), 64-bit offsets and fp32.  Block widths 256 (many blocks), 4096 and the default."""
+def block_kernel_operands():
+    """(A, B) of check_spgemm_block_kernel"""
     rng = np.random.default_rng(23)
     n, k = 2600, 9000 + 37
     lens = rng.integers(0, 40, size=n); lens[:6] = (k, 3000, 2500, 0, 1, 700); lens[-1] = 1501
@@ -819,6 +831,16 @@ def check_spgemm_block_kernel(be):
             np.sort(rng.choice(n, size=600, replace=False))]
     arm = np.zeros(len(rows) + 1, dtype=np.int64); np.cumsum([len(r) for r in rows], out=arm[1:])
     A = oracle.Crs(len(rows), n, arm, np.concatenate(rows).astype(np.int32), 1 + 49 * rng.random(arm[-1]))
+    return A, B
+
+
+def check_spgemm_block_kernel(be):
+    """Column-block value kernel (round 5, `spgemm_block`): rows of C that are dense, or have more lists than the flat kernel's shapes
+    hold, accumulate per (row, column block) in a direct-indexed LDS accumulator, with the pieces of every list taken from an index of
+    B.  Cases: k not a multiple of the block width, blocks with no entry of a row, an A row of 2500 lists (three chunks of lists into
+    one accumulator), a row that is 100 % dense, lists that end B's arrays (guarded 16-byte loads), empty B rows inside an A row,
+    numeric reuse (the index of B is kept), 64-bit offsets and fp32.  Block widths 256 (many blocks), 4096 and the default."""
+    A, B = block_kernel_operands()
     try:
         # items: groups of blocks with a position-indexed accumulator (cap: entries per group; 64 forces the dense blocks to stay column-indexed
         # items next to groups), or (items 0) one workgroup per (row, block)
@@ -862,12 +884,8 @@ def check_spgemm_block_kernel(be):
         kk._capi.check(be.lib, be.lib.kkamd_set_default(b"spgemm_item_cap", 6144))
 
 
-def check_spgemm_val_steps(be):
-    """Flat value kernel (vector walk: units of eight entries of one list, 16-byte loads) on rows of C whose windows hold several steps of
-    products (lists that overlap heavily), in the lightest shape (128 work-items), the 512-work-item shape (more than 256 lists) and next to
-    rows whose windows end inside the first step.  The last row of B is one of the long lists and nnz(B) is not a multiple of 4: the 16-byte
-    walks of the symbolic phase (unit kernel) and of the bitmap kernel take the array's last, partial quad from their tail registers.
-    (The scalar walks with 1 .. 3 steps in flight, knob spgemm_val_steps, measured neutral in round 5, are gone in round 6.)"""
+def val_steps_operands():
+    """A and [(last_len, B)] of check_spgemm_val_steps: the last row of B has last_len entries (nnz(B) is no multiple of 4)"""
     rng = np.random.default_rng(17)
     n, k = 400, 12000
     rows = [list(range(23)) + [n - 1],                    # 24 lists of ~6000 over 12000 columns: ~12 products per entry of C
@@ -882,8 +900,17 @@ def check_spgemm_val_steps(be):
         rm = np.zeros(n + 1, dtype=np.int64); np.cumsum(lens, out=rm[1:])
         ent = np.concatenate([np.sort(rng.choice(k, size=l, replace=False)) for l in lens]).astype(np.int32)
         return oracle.Crs(n, k, rm, ent, 1 + 49 * rng.random(rm[-1]))
-    for last_len in (6001, 6007, 6002):
-        B = make_b(last_len)
+    return A, [(last_len, make_b(last_len)) for last_len in (6001, 6007, 6002)]
+
+
+def check_spgemm_val_steps(be):
+    """Flat value kernel (vector walk: units of eight entries of one list, 16-byte loads) on rows of C whose windows hold several steps of
+    products (lists that overlap heavily), in the lightest shape (128 work-items), the 512-work-item shape (more than 256 lists) and next to
+    rows whose windows end inside the first step.  The last row of B is one of the long lists and nnz(B) is not a multiple of 4: the 16-byte
+    walks of the symbolic phase (unit kernel) and of the bitmap kernel take the array's last, partial quad from their tail registers.
+    (The scalar walks with 1 .. 3 steps in flight, knob spgemm_val_steps, measured neutral in round 5, are gone in round 6.)"""
+    A, Bs = val_steps_operands()
+    for last_len, B in Bs:
         assert B.nnz % 4 == last_len % 4 != 0
         got = check_spgemm(be, A, B)
         assert np.diff(got.row_map)[0] > 5461
@@ -894,10 +921,8 @@ def check_spgemm_val_steps(be):
     check_spgemm(be, A, B, offset_dtype=np.int64, value_dtype=np.float32)
 
 
-def check_spgemm_sorted_emission(be):
-    """Rows of C with more than 256 entries out of at most 2048 products: entries(C) sorted in LDS (`spgemm_emit_sort`, default) instead
-    of walking the products through a 2^20-column bitmap.  A rows of more than 256 entries (two chunks of lists), duplicates among
-    the products, rows above the product limit next to them (bitmap kernel), short rows (wave kernel); same C with the knob off."""
+def sorted_emission_operands():
+    """(A, B) of check_spgemm_sorted_emission"""
     rng = np.random.default_rng(23)
     nb, k = 3000, 50000
     lens = np.concatenate([np.full(1000, 3), np.full(2000, 20)])
@@ -916,6 +941,14 @@ def check_spgemm_sorted_emission(be):
     rows.append(np.concatenate([np.full(1, 1200), np.sort(rng.choice(np.arange(1000, 3000), size=30, replace=False))]))   # (unsorted A row, maybe a duplicate column)
     arm = np.zeros(len(rows) + 1, dtype=np.int64); np.cumsum([len(r) for r in rows], out=arm[1:])
     A = oracle.Crs(len(rows), nb, arm, np.concatenate(rows).astype(np.int32), 1 + 49 * rng.random(arm[-1]))
+    return A, B
+
+
+def check_spgemm_sorted_emission(be):
+    """Rows of C with more than 256 entries out of at most 2048 products: entries(C) sorted in LDS (`spgemm_emit_sort`, default) instead
+    of walking the products through a 2^20-column bitmap.  A rows of more than 256 entries (two chunks of lists), duplicates among
+    the products, rows above the product limit next to them (bitmap kernel), short rows (wave kernel); same C with the knob off."""
+    A, B = sorted_emission_operands()
     gold = oracle.spgemm(A, B)
     sizes = np.diff(gold.row_map)
     assert (sizes[:42] > 256).all()
@@ -941,10 +974,8 @@ def check_spgemm_sorted_emission(be):
             kk._capi.check(be.lib, be.lib.kkamd_set_default(b"spgemm_emit_sort", 1))
 
 
-def check_spgemm_quad_rows(be):
-    """Wave-per-row kernels with four rows of the list per wave (`spgemm_quad_rows`): stencil products whose rows all have a few
-    dozen products (16 lanes per row), lists whose length is no multiple of four, waves that mix small and larger rows (they fall back to
-    one row after the other), A rows of more than 16 entries on 1-entry rows of B (two chunks per group), empty rows; same C with the knob off."""
+def quad_rows_cases():
+    """[(A, B)] of check_spgemm_quad_rows; the first is the 7-point stencil squared"""
     rng = np.random.default_rng(29)
     cases = []
     A7 = randomized(oracle.laplace3d("FD", 9, 7, 5)); cases.append((A7, A7))                      # 315 rows, 49 products at most
@@ -968,6 +999,15 @@ def check_spgemm_quad_rows(be):
     arm = np.zeros(len(rows) + 1, dtype=np.int64); np.cumsum([len(r) for r in rows], out=arm[1:])
     Am = oracle.Crs(len(rows), nb, arm, np.concatenate(rows).astype(np.int32), 1 + 49 * rng.random(arm[-1]))
     cases.append((Am, B1))
+    return cases
+
+
+def check_spgemm_quad_rows(be):
+    """Wave-per-row kernels with four rows of the list per wave (`spgemm_quad_rows`): stencil products whose rows all have a few
+    dozen products (16 lanes per row), lists whose length is no multiple of four, waves that mix small and larger rows (they fall back to
+    one row after the other), A rows of more than 16 entries on 1-entry rows of B (two chunks per group), empty rows; same C with the knob off."""
+    cases = quad_rows_cases()
+    A7 = cases[0][0]
     try:
         for on in (2, 1, 0):         # 2: always (waves with a larger row fall back), 1: only when every row of the product is small (default), 0: never
             kk._capi.check(be.lib, be.lib.kkamd_set_default(b"spgemm_quad_rows", on))
@@ -976,6 +1016,36 @@ def check_spgemm_quad_rows(be):
             check_spgemm(be, A7, A7, offset_dtype=np.int64, value_dtype=np.float32)
     finally:
         kk._capi.check(be.lib, be.lib.kkamd_set_default(b"spgemm_quad_rows", 1))
+
+
+def all_bins_operands():
+    """(A, B) of test_spgemm_all_bins: rows landing in every launch shape of both phases: flops 0 / <=1365 / <=2048 / <=16384 / dense,
+    and nnz(C row) <=256 / <=2048 / <=5461 / dense; row 6 is the union of three hub rows (dense path with overlapping columns)"""
+    B0 = hub_matrix(64, 30000, 40, {0: 9000, 1: 3000, 2: 600, 3: 120, 5: 20000}, seed=1)
+    rng = np.random.default_rng(2)
+    cols_for = {0: [0], 1: [1], 2: [2], 3: [3, 7], 4: [], 5: [5], 6: [0, 1, 5], 7: list(range(6, 36))}
+    rm = [0]; ent = []
+    for i in range(8):
+        ent += cols_for[i]; rm.append(len(ent))
+    A0 = oracle.Crs(8, 64, np.array(rm), np.array(ent, dtype=np.int32), 1 + 49 * rng.random(len(ent)))
+    return A0, B0
+
+
+def dense_row_windows_operands():
+    """(A0, B0, A1, B1, A2, B2, rng) of test_spgemm_dense_row_windows: hub rows of B under short rows of A; an A row of 650 entries (longer than
+    the LDS cursor cache of 512); an A row of 2500 entries (above the row-flops pass's workgroup-per-row threshold) next to short ones"""
+    B0 = hub_matrix(48, 26000, 25, {0: 9000, 1: 7000, 2: 12000, 3: 300}, seed=11)
+    rm = [0, 3, 4, 8, 8, 11]
+    ent = np.array([0, 1, 2,   2,   0, 3, 5, 9,   1, 2, 30], dtype=np.int32)
+    rng = np.random.default_rng(3)
+    A0 = oracle.Crs(5, 48, np.array(rm), ent, 1 + 49 * rng.random(len(ent)))
+    B1 = randomized(oracle.random_crs(700, 20000, 12, variance=6, seed=21, sorted_rows=True))
+    cols = np.sort(rng.choice(700, size=650, replace=False)).astype(np.int32)
+    A1 = oracle.Crs(2, 700, np.array([0, 650, 653]), np.concatenate([cols, [1, 5, 9]]).astype(np.int32), 1 + 49 * rng.random(653))
+    B2 = randomized(oracle.random_crs(3000, 5000, 3, variance=2, seed=22, sorted_rows=True))
+    cols2 = np.sort(rng.choice(3000, size=2500, replace=False)).astype(np.int32)
+    A2 = oracle.Crs(3, 3000, np.array([0, 2, 2502, 2505]), np.concatenate([[4, 7], cols2, [1, 5, 9]]).astype(np.int32), 1 + 49 * rng.random(2505))
+    return A0, B0, A1, B1, A2, B2, rng
 
 
 def randomized(A0, seed=5):
@@ -995,6 +1065,428 @@ def hub_matrix(n, ncols, base_nnz, hubs, seed=0):
     for i in range(n):
         ent[rm[i]:rm[i + 1]] = np.sort(rng.choice(ncols, size=lens[i], replace=False))
     return oracle.Crs(n, ncols, rm, ent, 1 + 49 * rng.random(rm[-1]))
+
+
+# ------------------------------------------------------------------------------------------- SpGEMM: values, exactly
+# check_spgemm compares values with the reference's relative comparator (1e-7 / 3.7e-3 on non-negative inputs).  The checks below
+# compare them with a plain numpy reference of their own (spgemm_by_products, long-double sums), bit for bit where the inputs make
+# every partial sum exactly representable (check_spgemm_exact) and within the textbook bound where they do not (mode "bound"), and
+# read the library's "verbose" lines to prove which value kernel every case reached.
+U_ROUND = {np.dtype(np.float64): 2.0 ** -53, np.dtype(np.float32): 2.0 ** -24}
+P_BITS = {np.dtype(np.float64): 53, np.dtype(np.float32): 24}
+# the numeric phase's bins (first "verbose" line) and its value kernels (second line), in the order the library prints them
+BIN_COUNTS = ("wave hash", "block hash small", "block hash large", "dense rows", "column blocks", "LDS value windows", "LDS hub windows", "HBM accumulator")
+VALUE_KERNELS = ("quad", "wave", "block_small", "block_large", "items_rank", "items_direct", "blocks_wg", "win128", "win256", "win512", "win1024",
+                 "hub", "hub_multi", "hbm")
+KNOB_DEFAULTS = {"spgemm_block_w": 16384, "spgemm_items": 1, "spgemm_item_cap": 6144, "spgemm_quad_rows": 1, "spgemm_force_unsorted": 0,
+                 "spgemm_val_cap": 2048, "spgemm_unit_bits": 18, "spgemm_win_bits": 1 << 20, "spgemm_emit_sort": 1, "spgemm_block": 1}
+
+
+class ProductsOf:
+    """the expanded products of A * B, stable-sorted by (row, column): which entry of A and of B makes each product, where every entry of C
+    begins, and the structure of C (row_map int64, entries int32, n = products per entry)"""
+
+    def __init__(self, A0, B0):
+        assert A0.ncols == B0.nrows
+        lenB = np.diff(B0.row_map)
+        cnt = lenB[A0.entries] if A0.nnz else np.zeros(0, dtype=np.int64)           # products of every entry of A
+        total = int(cnt.sum())
+        self.a_idx = np.repeat(np.arange(A0.nnz, dtype=np.int64), cnt)
+        begin = np.cumsum(cnt) - cnt
+        self.b_idx = np.repeat(B0.row_map[:-1][A0.entries] - begin, cnt) + np.arange(total, dtype=np.int64) if total else np.zeros(0, dtype=np.int64)
+        row_of_a = np.repeat(np.arange(A0.nrows, dtype=np.int64), np.diff(A0.row_map))
+        rows = row_of_a[self.a_idx]
+        key = rows * np.int64(max(B0.ncols, 1)) + B0.entries[self.b_idx]
+        order = np.argsort(key, kind="stable")
+        self.a_idx, self.b_idx, key = self.a_idx[order], self.b_idx[order], key[order]
+        self.first = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]])) if total else np.zeros(0, dtype=np.int64)
+        self.n = np.diff(np.concatenate([self.first, [total]])).astype(np.int64)
+        self.entries = (key[self.first] % max(B0.ncols, 1)).astype(np.int32)
+        self.row_map = np.zeros(A0.nrows + 1, dtype=np.int64)
+        np.cumsum(np.bincount(key[self.first] // max(B0.ncols, 1), minlength=A0.nrows), out=self.row_map[1:])
+        self.n_max = int(self.n.max()) if total else 0
+
+    def reduce(self, valA, valB):
+        """per entry of C: (sum of its products, S = sum of their magnitudes), accumulated in np.longdouble in the sorted order"""
+        assert np.finfo(np.longdouble).nmant > np.finfo(np.float64).nmant, "np.longdouble is no wider than float64 here"
+        if not self.first.size:
+            return np.zeros(0, dtype=np.longdouble), np.zeros(0, dtype=np.longdouble)
+        with np.errstate(invalid="ignore", over="ignore"):
+            prod = valA.astype(np.longdouble)[self.a_idx] * valB.astype(np.longdouble)[self.b_idx]
+            return np.add.reduceat(prod, self.first), np.add.reduceat(np.abs(prod), self.first)
+
+
+def spgemm_by_products(A0, B0):
+    """C = A * B by its definition, independent of the oracle: every product (row, column, a * b) expanded, stable-sorted by (row, column) and
+    reduced per entry in np.longdouble.  Rows of A and B need not be sorted and may hold a column several times (every pair of duplicates
+    contributes its own product).  Returns (row_map, entries, sums, n, S): C's structure as the library writes it (rows column-sorted, every
+    structural entry kept, a sum that cancels included) and per entry the sum, the number of products and S = sum |a * b|."""
+    P = ProductsOf(A0, B0)
+    sums, S = P.reduce(np.asarray(A0.values, dtype=np.float64), np.asarray(B0.values, dtype=np.float64))
+    return P.row_map, P.entries, sums, P.n, S
+
+
+def value_bits(n_max, value_dtype):
+    """b: with values that are integers below 2^b times a fixed power of two, a product has at most 2b bits and a sum of at most n_max
+    products 2b + ceil(log2 n_max): while that is at most P - 1 every partial sum, in any order, fused or not, is exactly representable"""
+    return min(20, (P_BITS[np.dtype(value_dtype)] - 1 - int(math.ceil(math.log2(max(n_max, 1))))) // 2)
+
+
+def exact_values(rng, size, b):
+    """signed integers of at most b bits (never zero) times 2^-4"""
+    mag = rng.integers(1, 1 << b, size=size).astype(np.float64)
+    return np.where(rng.random(size) < 0.5, -mag, mag) * 2.0 ** -4
+
+
+def _with_values(A0, values):
+    return oracle.Crs(A0.nrows, A0.ncols, A0.row_map, A0.entries, values)
+
+
+CANCEL_KEEP = 4          # cancelling mode: columns c with c % CANCEL_KEEP == 1 keep re-drawn values, the others cancel
+
+
+def cancelling_pair(A0, B0):
+    """the structures A' = [A A] (every row's entries, then the same entries n columns further) and B' = B stacked on a copy of B"""
+    lenA = np.diff(A0.row_map)
+    pos = np.arange(A0.nnz, dtype=np.int64)
+    row = np.repeat(np.arange(A0.nrows, dtype=np.int64), lenA)
+    within = pos - A0.row_map[:-1][row]
+    dst1 = 2 * A0.row_map[:-1][row] + within
+    dst2 = dst1 + lenA[row]
+    ent = np.empty(2 * A0.nnz, dtype=np.int32)
+    ent[dst1] = A0.entries; ent[dst2] = A0.entries + A0.ncols
+    A2 = oracle.Crs(A0.nrows, 2 * A0.ncols, 2 * A0.row_map, ent, np.zeros(2 * A0.nnz))
+    rmB = np.concatenate([B0.row_map, B0.row_map[1:] + B0.row_map[-1]])
+    B2 = oracle.Crs(2 * B0.nrows, B0.ncols, rmB, np.concatenate([B0.entries, B0.entries]), np.zeros(2 * B0.nnz))
+    return A2, B2, dst1, dst2
+
+
+SPECIALS = (0.0, np.inf, -np.inf, np.nan)
+
+
+def special_positions(rng, A0, extra):
+    """positions of the array that get a special value: its first and last entry, the first and the last entry of a row in the middle and of
+    the longest row, and `extra` random ones"""
+    if A0.nnz == 0:
+        return np.zeros(0, dtype=np.int64)
+    lens = np.diff(A0.row_map)
+    rows = np.flatnonzero(lens)
+    mid, longest = rows[len(rows) // 2], int(np.argmax(lens))
+    pos = [0, A0.nnz - 1, A0.row_map[mid], A0.row_map[mid + 1] - 1, A0.row_map[longest], A0.row_map[longest + 1] - 1]
+    pos += list(rng.integers(0, A0.nnz, size=extra))
+    return np.array(pos, dtype=np.int64)
+
+
+def parse_numeric_verbose(out):
+    """({bin: rows}, {value kernel: rows}) of the last numeric call's two "verbose" lines in `out`"""
+    bins = re.findall(r"kkamd spgemm numeric \((\w+)\): rows per kernel -- (.*)", out)
+    kern = re.findall(r"kkamd spgemm numeric \((\w+)\): rows per value kernel -- (.*)", out)
+    assert bins and kern, "no verbose lines of the numeric phase in: %r" % out[-400:]
+    nums = [int(v) for v in re.findall(r"\d+", bins[-1][1])]
+    assert len(nums) == len(BIN_COUNTS), bins[-1]
+    kd = {k_: int(v_) for k_, v_ in re.findall(r"(\w+)=(\d+)", kern[-1][1])}
+    assert set(kd) == set(VALUE_KERNELS) | {"blocks"}, kern[-1]
+    kd["dense_alg"] = int(kern[-1][0] == "SPGEMM_KK_DENSE")
+    return dict(zip(BIN_COUNTS, nums)), kd
+
+
+class Coverage:
+    """which bins and value kernels a set of cases has reached, and (mode "bound") the largest error / bound seen next to each kernel"""
+
+    def __init__(self):
+        self.bins = {k_: 0 for k_ in BIN_COUNTS}
+        self.kernels = {k_: 0 for k_ in VALUE_KERNELS + ("dense_alg", "emit_sorted")}
+        self.ratio = {k_: 0.0 for k_ in VALUE_KERNELS + ("dense_alg",)}
+
+    def add(self, bins, kernels, ratio=None):
+        for k_, v_ in bins.items(): self.bins[k_] += v_
+        for k_, v_ in kernels.items():
+            self.kernels[k_] += v_
+            if v_ and ratio is not None and k_ in self.ratio: self.ratio[k_] = max(self.ratio[k_], ratio)
+
+    def assert_complete(self, what):
+        missing = [k_ for k_, v_ in self.bins.items() if not v_] + [k_ for k_, v_ in self.kernels.items() if not v_]
+        assert not missing, "%s: no case reached %s (bins %r, kernels %r)" % (what, missing, self.bins, self.kernels)
+
+
+def check_spgemm_exact(be, A0, B0, mode="signed", offset_dtype=np.int32, value_dtype=np.float64, algo="SPGEMM_KK", knobs=None, capfd=None,
+                       expect=(), coverage=None, seed=0, name=""):
+    """C = A * B on the STRUCTURE of A0 and B0 with values drawn here, against spgemm_by_products.  Structure bit for bit; values by mode:
+      signed      signed integers of b bits times 2^-4, b from the case (value_bits): every order of summation gives the same bits: `==`
+      cancelling  A' = [A A], B' = B over a copy of B whose values are the negated ones in three columns out of four: those entries of C are
+                  sums of at least two products that are exactly zero -- they must be present and hold 0; at least a tenth of nnz(C) are
+                  such; everything else `==`
+      special     +Inf, -Inf, NaN and stored 0.0 written into A and B (first / last entry of the arrays and of rows among them): NaN where the
+                  reference has NaN, the same infinity where it has one, `==` elsewhere; then numeric reuse on the same handle with finite
+                  values must be `==` again (nothing non-finite may survive in a table, an accumulator or a store)
+      bound       signed real values, uniform in (-50, 50) and rounded to the value type: |C - reference| <= gamma_(n+1) S per entry, gamma_m =
+                  m u / (1 - m u), u the unit roundoff of the value type, n and S the entry's number of products and sum of |a * b| -- the bound
+                  of any order of summation of n rounded products (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., section 3.1), plus
+                  the reference's own error (the same expression with the long double's unit roundoff)
+    knobs: process-wide defaults set for the case and restored.  capfd: the library's verbose lines are read, the rows per bin and value kernel
+    are added to `coverage`, and every kernel named in `expect` must have taken rows.  Returns the largest error / bound (mode "bound") or 0."""
+    vdt = np.dtype(value_dtype)
+    rng = np.random.default_rng([seed, 17])
+    if mode == "cancelling":
+        A0, B0, dst1, dst2 = cancelling_pair(A0, B0)
+    P = ProductsOf(A0, B0)
+    b = value_bits(P.n_max, vdt)
+    assert b >= (13 if vdt == np.float64 else 3), "%s: %d products meet in one entry: %d-bit values cannot tell a rounding apart" % (name, P.n_max, b)
+
+    def draw():
+        if mode == "bound":
+            return (rng.uniform(-50, 50, A0.nnz).astype(vdt).astype(np.float64), rng.uniform(-50, 50, B0.nnz).astype(vdt).astype(np.float64))
+        va, vb = exact_values(rng, A0.nnz, b), exact_values(rng, B0.nnz, b)
+        if mode == "cancelling":
+            half = B0.nnz // 2
+            va[dst2] = va[dst1]
+            cancels = B0.entries[:half] % CANCEL_KEEP != 1
+            vb[half:][cancels] = -vb[:half][cancels]
+        return va, vb
+    va, vb = draw()
+    if mode == "special":
+        for v, M in ((va, A0), (vb, B0)):
+            pos = special_positions(rng, M, extra=min(48, 2 + M.nnz // 64))
+            v[pos] = np.array(SPECIALS)[np.arange(len(pos)) % 4]
+    assert np.array_equal(va.astype(vdt).astype(np.float64), va, equal_nan=True) and np.array_equal(vb.astype(vdt).astype(np.float64), vb, equal_nan=True)
+    if knobs:
+        for k_, v_ in knobs.items(): kk._capi.check(be.lib, be.lib.kkamd_set_default(k_.encode(), v_))
+    try:
+        A, B = dev(be, _with_values(A0, va), offset_dtype, vdt), dev(be, _with_values(B0, vb), offset_dtype, vdt)
+        kh = kk.KokkosKernelsHandle(be)
+        kh.create_spgemm_handle(algo)
+        sh = kh.get_spgemm_handle()
+        Cm = kk.spgemm_symbolic(kh, A, False, B, False)
+        assert np.array_equal(be.to_numpy(Cm.graph.row_map).astype(np.int64), P.row_map), name + ": symbolic row_map differs from the products'"
+        if capfd is not None:
+            capfd.readouterr(); sh.set("verbose", 1)
+        kk.spgemm_numeric(kh, A, False, B, False, Cm)
+        if capfd is not None:
+            sh.set("verbose", 0)
+            bins, kernels = parse_numeric_verbose(capfd.readouterr().out)
+            assert kernels["dense_alg"] == int(sh.get(8) == 1)
+            kernels["emit_sorted"] = sh.get(15)                          # rows whose entries(C) were sorted in LDS (a structure kernel; the handle counts it)
+            blocks = kernels.pop("blocks")                                # the handle's own queries say the same
+            assert blocks == (sh.get(16) if bins["dense rows"] else 0) == bins["column blocks"], (kernels, sh.get(16))
+            if blocks and not kernels["blocks_wg"]: assert (kernels["items_rank"], kernels["items_direct"]) == (sh.get(17), sh.get(18)), (kernels, sh.get(17), sh.get(18))
+            for k_ in expect:                                             # a dict: exactly that many rows
+                assert kernels[k_] == expect[k_] if isinstance(expect, dict) else kernels[k_] > 0, "%s: rows of the value kernel %r: %r" % (name, k_, kernels)
+        ratio = _compare_exact(P, va, vb, Cm, mode, vdt, name)
+        if mode == "special":                                       # numeric reuse: finite values into the same arrays of A and B's graph, same handle, same C
+            va2, vb2 = exact_values(rng, A0.nnz, b), exact_values(rng, B0.nnz, b)
+            A2 = kk.CrsMatrix(A0.nrows, A0.ncols, A.graph.row_map, A.graph.entries, be.from_numpy(va2.astype(vdt)), backend=be)
+            B2 = kk.CrsMatrix(B0.nrows, B0.ncols, B.graph.row_map, B.graph.entries, be.from_numpy(vb2.astype(vdt)), backend=be)
+            kk.spgemm_numeric(kh, A2, False, B2, False, Cm)
+            _compare_exact(P, va2, vb2, Cm, "signed", vdt, name + " (numeric reuse after the special values)")
+        kh.destroy_spgemm_handle()
+    finally:
+        if knobs:
+            for k_ in knobs: kk._capi.check(be.lib, be.lib.kkamd_set_default(k_.encode(), KNOB_DEFAULTS[k_]))
+    if capfd is not None and coverage is not None:
+        coverage.add(bins, kernels, ratio if mode == "bound" else None)
+    return ratio
+
+
+def _compare_exact(P, va, vb, Cm, mode, vdt, name):
+    rm, ent, val = Cm.to_host()
+    nnz = int(P.row_map[-1])
+    assert np.array_equal(rm.astype(np.int64), P.row_map), name + ": row_map differs"
+    assert np.array_equal(ent[:nnz], P.entries), name + ": entries differ"
+    got = val[:nnz].astype(np.float64)
+    sums, S = P.reduce(va, vb)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ref = sums.astype(np.float64)
+
+    def first_bad(bad):
+        i = int(np.flatnonzero(bad)[0]); r = int(np.searchsorted(P.row_map, i, side="right") - 1)
+        return "%d entries, first at row %d column %d (%d products): %r, reference %r" % (int(bad.sum()), r, int(P.entries[i]), int(P.n[i]), got[i], ref[i])
+    if mode == "bound":
+        u = U_ROUND[vdt]; ul = float(np.finfo(np.longdouble).eps) / 2
+        m = (P.n + 1).astype(np.longdouble)
+        bound = (m * u / (1 - m * u) + m * ul / (1 - m * ul)) * S
+        err = np.abs(got.astype(np.longdouble) - sums)
+        bad = ~(err <= bound)
+        assert not bad.any(), name + ": outside the bound gamma_(n+1) S: " + first_bad(bad)
+        return float((err / bound).max()) if nnz else 0.0
+    assert (ref == sums).all() or mode == "special", name + ": the reference's sums are not representable in float64 (the case's b is wrong)"
+    if mode == "special":
+        nan = np.isnan(ref)
+        assert nan.any() and np.isinf(ref).any() and (np.isfinite(ref).sum() >= nnz // 8), name + ": the special values reach %d NaN, %d Inf of %d entries" % (int(nan.sum()), int(np.isinf(ref).sum()), nnz)
+        bad = np.isnan(got) != nan
+        assert not bad.any(), name + ": NaN positions differ: " + first_bad(bad)
+        fin = np.isfinite(ref)
+        assert ((ref == sums) | ~fin).all(), name + ": a finite reference sum is not representable in float64"
+        bad = ~nan & (got != ref)
+        assert not bad.any(), name + ": values differ (Inf or finite entries): " + first_bad(bad)
+        return 0.0
+    bad = got != ref
+    assert not bad.any(), name + ": values differ: " + first_bad(bad)
+    if mode == "cancelling":
+        zero = P.entries % CANCEL_KEEP != 1
+        assert (P.n[zero] >= 2).all() and (ref[zero] == 0).all() and zero.sum() * 10 >= nnz > 0, name + ": %d cancelling entries of %d" % (int(zero.sum()), nnz)
+        assert (got[zero] == 0).all()
+    return 0.0
+
+
+def limit_operands(seed=41):
+    """(A, B): rows exactly at the limits the numeric dispatcher uses.  B has a million columns (no row of C is dense enough for the column-block
+    class): rows 0 .. 999 of exactly 8 entries, rows 1000 .. 2999 of exactly 1 entry in columns of their own, the others 1 .. 3 entries.
+    Rows of A: 256 / 257 one-entry lists (256 / 257 entries of C: wave table / dense bin); 32 / 33 one-entry lists (four rows per wave / one);
+    8 eight-entry lists (64 products) and one more one-entry list (65); 128 / 129 eight-entry lists (value windows of 128 / 256 work-items); 256 eight-entry lists (2048 products) and one more (2049); 512 / 513,
+    1024 / 1025 and 4096 / 4097 entries (value windows of 512 and of 1024 work-items, hub kernel in one pass and in two), 9000 (three passes),
+    3 entries and none."""
+    rng = np.random.default_rng(seed)
+    nB, k = 14000, 1000003
+    lens = rng.integers(1, 4, size=nB); lens[:1000] = 8; lens[1000:3000] = 1
+    rm = np.zeros(nB + 1, dtype=np.int64); np.cumsum(lens, out=rm[1:])
+    ent = np.concatenate([np.sort(rng.choice(k, size=l, replace=False)) for l in lens]).astype(np.int32)
+    ent[rm[1000]:rm[3000]] = rng.choice(k, size=2000, replace=False)
+    B = oracle.Crs(nB, k, rm, ent, np.ones(rm[-1]))
+    ones, eights, rest = np.arange(1000, 3000), np.arange(0, 1000), np.arange(3000, nB)
+    pick = lambda pool, c: np.sort(rng.choice(pool, size=c, replace=False))
+    rows = [pick(eights, 128), pick(eights, 129), pick(ones, 256), pick(ones, 257), pick(ones, 32), pick(ones, 33), pick(eights, 8), np.concatenate([pick(eights, 8), pick(ones, 1)]),
+            pick(eights, 256), np.concatenate([pick(eights, 256), pick(ones, 1)]), pick(rest, 512), pick(rest, 513), pick(rest, 1024), pick(rest, 1025),
+            pick(rest, 4096), pick(rest, 4097), pick(rest, 9000), pick(rest, 3), np.array([], dtype=np.int64)]
+    arm = np.zeros(len(rows) + 1, dtype=np.int64); np.cumsum([len(r) for r in rows], out=arm[1:])
+    A = oracle.Crs(len(rows), nB, arm, np.concatenate(rows).astype(np.int32), np.ones(arm[-1]))
+    return A, B
+
+
+def unsorted_rows(B0, seed=3):
+    """B0 with the entries of every row in a random order"""
+    rng = np.random.default_rng(seed)
+    ent = B0.entries.copy()
+    for i in range(B0.nrows):
+        lo, hi = B0.row_map[i], B0.row_map[i + 1]
+        ent[lo:hi] = ent[lo:hi][rng.permutation(hi - lo)]
+    return oracle.Crs(B0.nrows, B0.ncols, B0.row_map, ent, B0.values)
+
+
+def exact_cases(light=False):
+    """[(name, A, B, algo, knobs, value kernels the case must reach, or {kernel: rows})]: the structures of the SpGEMM checks of this file, with the knob settings
+    those checks use, and rows at the dispatcher's limits.  light: the small ones (the SIMT emulator spends seconds on a wide bitmap)."""
+    import fuzz_cases as fz
+    KK, DENSE = "SPGEMM_KK", "SPGEMM_KK_DENSE"
+    cases = []
+    add = lambda name, A, B, expect, algo=KK, knobs=None: cases.append((name, A, B, algo, knobs, expect if isinstance(expect, dict) else tuple(expect)))
+    L = oracle.laplace3d("FE", 6, 5, 4) if light else oracle.laplace3d("FE", 10, 10, 10)
+    add("27-pt squared", L, L, ["wave"])
+    quad = quad_rows_cases()
+    add("7-pt squared, four rows per wave", quad[0][0], quad[0][1], ["quad"])               # every row at most 32 entries: the rule leaves no other kernel
+    add("mixed small and long rows, quad_rows 1", quad[3][0], quad[3][1], ["quad", "wave"])
+    add("A P, quad_rows 2", quad[2][0], quad[2][1], ["quad"], knobs={"spgemm_quad_rows": 2})
+    add("9-pt squared, quad_rows 0", quad[1][0], quad[1][1], ["wave"], knobs={"spgemm_quad_rows": 0})
+    A1 = oracle.random_crs(100, 50, 8, seed=5); B1 = oracle.random_crs(50, 160, 30, seed=6)
+    add("duplicate columns in rows of A and of B, unsorted", A1, B1, ["wave"])
+    _, _, R, AP = galerkin_operands(8 if light else 12)
+    add("Galerkin R (A P)", R, AP, ["quad"])
+    Ld = oracle.laplace3d("FE", 5, 4, 3) if light else oracle.laplace3d("FE", 7, 6, 5)
+    add("dense accumulator: 27-pt squared", Ld, Ld, ["hbm", "dense_alg"], algo=DENSE)
+    add("dense accumulator: hub row of A", hub_matrix(30, 2000, 6, {3: 700}, seed=2), oracle.random_crs(2000, 1500, 10, variance=4, seed=7, sorted_rows=True),
+        ["hbm", "dense_alg"], algo=DENSE)
+    A, B = limit_operands()
+    # 32 lists and 3 | 33, 64 / 65 products, 256 | 128 x 8 | 129 x 8, 256 x 8 | 257, 256 x 8 + 1, 512 | 513, 1024 | 1025, 4096, 4097, 9000 | of which 4097, 9000
+    add("rows at the dispatcher's limits", A, B, {"quad": 2, "wave": 4, "win128": 1, "win256": 2, "win512": 3, "win1024": 2, "hub": 4, "hub_multi": 2})
+    A0, B0, A1w, B1w, A2w, B2w, _ = dense_row_windows_operands()
+    add("A row of 650 entries", A1w, B1w, ["wave", "items_rank"])                           # more than 512 lists and 3 % of the columns: column blocks
+    add("A row of 2500 entries", A2w, B2w, ["quad", "items_rank"])
+    add("A row of 650 entries, column blocks off", A1w, B1w, ["wave", "win1024"], knobs={"spgemm_block": 0})
+    add("A row of 2500 entries, column blocks off", A2w, B2w, ["quad", "hub"], knobs={"spgemm_block": 0})
+    Ab, Bb = all_bins_operands()
+    add("all bins, B unsorted", Ab, unsorted_rows(Bb), ["wave", "block_small", "block_large", "hbm"])
+    Au = oracle.random_crs(60, 150, 20, seed=9); Bu = fz.hubby(np.random.default_rng(12), 150, 9000, 8, 3, 6000, sort=False)
+    add("unsorted B with hub rows under duplicate-laden A", Au, Bu, ["hbm"])
+    if light:
+        return cases
+    rng = np.random.default_rng(66)
+    Al, Bl = fz.hubby(rng, 8, 4000, 3, 2, 3000), fz.hubby(rng, 4000, 30000, 6, 2, 2000)
+    add("long rows of A against hub rows of B", Al, Bl, ["quad", "items_rank", "items_direct"])
+    add("long rows of A against hub rows of B, column blocks off", Al, Bl, ["quad", "hub"], knobs={"spgemm_block": 0})
+    add("all bins", Ab, Bb, ["wave", "items_rank", "items_direct", "win128"])
+    add("hub rows of B", A0, B0, ["items_rank", "items_direct"])
+    add("hub rows of B, narrow windows, column blocks off", A0, B0, ["win128"], knobs={"spgemm_win_bits": 4096, "spgemm_val_cap": 192, "spgemm_block": 0})
+    add("hub rows of B, force_unsorted", A0, B0, ["hbm"], knobs={"spgemm_force_unsorted": 1})
+    A, B = block_kernel_operands()
+    for w, items, cap in ((256, 1, 6144), (256, 1, 64), (4096, 1, 1000), (256, 0, 6144), (16384, 1, 6144)):
+        add("column blocks w %d items %d cap %d" % (w, items, cap), A, B, ["quad", "blocks_wg"] if not items else (["items_rank", "items_direct"] if cap == 64 else ["items_rank"]),
+            knobs={"spgemm_block_w": w, "spgemm_items": items, "spgemm_item_cap": cap})
+    A, Bs = val_steps_operands()
+    add("lists that overlap heavily", A, Bs[0][1], ["items_rank", "items_direct"])
+    add("value windows with several steps (column blocks off)", A, Bs[0][1], ["win128", "win512"], knobs={"spgemm_block": 0})
+    A, B = sorted_emission_operands()
+    add("entries sorted in LDS", A, B, ["quad", "items_rank", "win128", "win512", "emit_sorted"])
+    A, B, Ad, Bd = kept_structure_operands()
+    add("kept bitmaps and lists", A, B, ["items_rank", "win128"])
+    add("dense rows of C", Ad, Bd, ["items_direct"])
+    units, _ = units_operands()
+    add("many short lists, units of 4096 columns", units[2][0], units[2][1], ["wave", "items_rank"], knobs={"spgemm_unit_bits": 12})
+    add("dense accumulator: random", oracle.random_crs(120, 900, 11, variance=6, seed=4, sorted_rows=True), oracle.random_crs(900, 700, 9, variance=5, seed=6, sorted_rows=True),
+        ["hbm", "dense_alg"], algo=DENSE)
+    Rm = oracle.rmat(9, 8, seed=7)
+    add("R-MAT scale 9 squared", Rm, Rm, ["quad", "wave", "items_rank"])
+    return cases
+
+
+TYPE_GRID = ((np.int32, np.float64), (np.int64, np.float32), (np.int64, np.float64), (np.int32, np.float32))
+
+
+def check_spgemm_values(be, capfd, mode, value_dtype, light=False, both_offsets=None):
+    """every case of exact_cases in one mode and value type (both offset types in mode "signed", the case's number deciding otherwise); the set
+    must reach every bin and every value kernel, the dense-accumulator algorithm included.  Mode "cancelling" works on other structures
+    ([A A] and B twice), so there the classes are reported and not required.  light: the small cases only, no requirement on the set.
+    Prints what it reached (and, in mode "bound", how much of the bound was used) when the last case is through."""
+    cov = Coverage(); lines = []; log = lines.append
+    if both_offsets is None: both_offsets = mode == "signed" and not light
+    for i, (name, A, B, algo, knobs, expect) in enumerate(exact_cases(light)):
+        odts = (np.int32, np.int64) if both_offsets else ((np.int32, np.int64)[(i + (value_dtype == np.float32)) % 2],)
+        for odt in odts:
+            tag = "%s [%s, %s, %s]" % (name, mode, np.dtype(odt).name, np.dtype(value_dtype).name)
+            ratio = check_spgemm_exact(be, A, B, mode, odt, value_dtype, algo, knobs, capfd, () if mode == "cancelling" else expect, cov, seed=i, name=tag)
+            if mode == "bound": log("%-90s largest error / bound %.3f" % (tag, ratio))
+    if mode == "bound":
+        log("largest error / bound among the cases that reached each value kernel (%s): %s" % (
+            np.dtype(value_dtype).name, ", ".join("%s %.3f" % (k_, v_) for k_, v_ in cov.ratio.items())))
+    log("rows per bin: %r\nrows (items) per value kernel: %r" % (cov.bins, cov.kernels))
+    print("\n".join(lines))
+    if mode != "cancelling" and not light:
+        cov.assert_complete("%s, %s" % (mode, np.dtype(value_dtype).name))
+    return cov
+
+
+def check_sort_and_merge_exact(be):
+    """sort_and_merge_matrix on exact signed values: sums bit for bit (any order gives the same bits), runs of duplicates that cancel to a
+    stored zero, fp32 values, both offset types, graph only (no values)"""
+    rng = np.random.default_rng(31)
+    lens = [20000, 3, 8193, 0, 700, 1, 40]
+    rm = np.zeros(len(lens) + 1, dtype=np.int64); np.cumsum(lens, out=rm[1:])
+    ent = rng.integers(0, 3000, size=rm[-1]).astype(np.int32)                   # about 7 copies of every column in the long row
+    for vdt, odt in ((np.float64, np.int32), (np.float32, np.int64)):
+        b = value_bits(64, vdt)
+        val = exact_values(rng, rm[-1], b)
+        for r in (0, 2, 4):                                                        # runs that cancel: every copy of these columns but the last holds v, the last -(count - 1) v
+            lo, hi = rm[r], rm[r + 1]
+            cols, cnt = np.unique(ent[lo:hi], return_counts=True)
+            for c in cols[(cnt >= 2) & (cols % 3 == 0)]:
+                at = lo + np.flatnonzero(ent[lo:hi] == c)
+                val[at[:-1]] = val[at[0]]
+                val[at[-1]] = -(len(at) - 1) * val[at[0]]
+        val = val.astype(vdt).astype(np.float64)
+        M = oracle.Crs(len(lens), 3000, rm, ent.copy(), val.astype(vdt))
+        Cm = kk.sort_and_merge_matrix(dev(be, M, odt))
+        r_, e_, v_ = Cm.to_host()
+        key = np.repeat(np.arange(len(lens), dtype=np.int64), lens) * 3000 + ent
+        order = np.argsort(key, kind="stable")
+        first = np.flatnonzero(np.concatenate([[True], key[order][1:] != key[order][:-1]]))
+        sums = np.add.reduceat(val.astype(np.longdouble)[order], first)
+        grm = np.zeros(len(lens) + 1, dtype=np.int64); np.cumsum(np.bincount(key[order][first] // 3000, minlength=len(lens)), out=grm[1:])
+        n = len(first)
+        assert np.array_equal(r_.astype(np.int64), grm) and np.array_equal(e_[:n], (key[order][first] % 3000).astype(np.int32))
+        assert (sums.astype(np.float64) == sums).all() and (sums == 0).sum() > 100, int((sums == 0).sum())
+        assert np.array_equal(v_[:n].astype(np.float64), sums.astype(np.float64)), "sort_and_merge: sums differ from the exact ones"
+        G = kk.CrsMatrix.from_host(len(lens), 3000, rm, ent.copy(), None, offset_dtype=odt, backend=be)          # graph only
+        Gm = kk.sort_and_merge_matrix(G)
+        r_, e_, v_ = Gm.to_host()
+        assert v_ is None and np.array_equal(r_.astype(np.int64), grm) and np.array_equal(e_[:n], (key[order][first] % 3000).astype(np.int32))
 
 
 # --- spmv_struct: the reference's own cases (sparse/unit_test/Test_Sparse_spmv.hpp:609-768, 1096-1104) -----------------

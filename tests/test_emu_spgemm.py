@@ -119,15 +119,7 @@ def test_spgemm_float(be):
 def test_spgemm_all_bins(be):
     # rows landing in every launch shape of both phases: flops 0 / <=1365 / <=2048 / <=16384 / dense,
     # and nnz(C row) <=256 / <=2048 / <=5461 / dense
-    B0 = pc.hub_matrix(64, 30000, 40, {0: 9000, 1: 3000, 2: 600, 3: 120, 5: 20000}, seed=1)
-    lens = {0: 1, 1: 1, 2: 1, 3: 2, 4: 0, 5: 1, 6: 3, 7: 30}
-    rng = np.random.default_rng(2)
-    rows = []
-    cols_for = {0: [0], 1: [1], 2: [2], 3: [3, 7], 4: [], 5: [5], 6: [0, 1, 5], 7: list(range(6, 36))}
-    rm = [0]; ent = []
-    for i in range(8):
-        ent += cols_for[i]; rm.append(len(ent))
-    A0 = oracle.Crs(8, 64, np.array(rm), np.array(ent, dtype=np.int32), 1 + 49 * rng.random(len(ent)))
+    A0, B0 = pc.all_bins_operands()
     got = pc.check_spgemm(be, A0, B0)
     sizes = np.diff(got.row_map)
     assert sizes[4] == 0 and sizes[3] <= 256 and 256 < sizes[2] <= 2048 and 2048 < sizes[1] <= 5461 and sizes[0] > 5461
@@ -141,19 +133,9 @@ def _set(be, key, value):
 def test_spgemm_dense_row_windows(be):
     # dense rows with (a) the column bitmap cut into several LDS windows, (b) small value windows so the per-entry
     # cursors are exercised across many passes, (c) the HBM-accumulator fallback taken when B is not sorted
-    B0 = pc.hub_matrix(48, 26000, 25, {0: 9000, 1: 7000, 2: 12000, 3: 300}, seed=11)
-    rm = [0, 3, 4, 8, 8, 11]
-    ent = np.array([0, 1, 2,   2,   0, 3, 5, 9,   1, 2, 30], dtype=np.int32)
-    rng = np.random.default_rng(3)
-    A0 = oracle.Crs(5, 48, np.array(rm), ent, 1 + 49 * rng.random(len(ent)))
-    # a row of A longer than the LDS cursor cache (512 entries): the HBM cursors carry the rest across windows
-    B1 = pc.randomized(oracle.random_crs(700, 20000, 12, variance=6, seed=21, sorted_rows=True))
-    cols = np.sort(rng.choice(700, size=650, replace=False)).astype(np.int32)
-    A1 = oracle.Crs(2, 700, np.array([0, 650, 653]), np.concatenate([cols, [1, 5, 9]]).astype(np.int32), 1 + 49 * rng.random(653))
-    # a row of A above the row-flops pass's workgroup-per-row threshold (2048 entries), next to short ones
-    B2 = pc.randomized(oracle.random_crs(3000, 5000, 3, variance=2, seed=22, sorted_rows=True))
-    cols2 = np.sort(rng.choice(3000, size=2500, replace=False)).astype(np.int32)
-    A2 = oracle.Crs(3, 3000, np.array([0, 2, 2502, 2505]), np.concatenate([[4, 7], cols2, [1, 5, 9]]).astype(np.int32), 1 + 49 * rng.random(2505))
+    # A1: a row of A longer than the LDS cursor cache (512 entries): the HBM cursors carry the rest across windows
+    # A2: a row of A above the row-flops pass's workgroup-per-row threshold (2048 entries), next to short ones
+    A0, B0, A1, B1, A2, B2, rng = pc.dense_row_windows_operands()
     pc.check_spgemm(be, A2, B2)
     pc.check_spgemm(be, A2, B2, offset_dtype=np.int64)
     try:
@@ -213,6 +195,21 @@ def test_spgemm_entries_sorted_in_lds(be):
 
 def test_spgemm_four_rows_per_wave(be):
     pc.check_spgemm_quad_rows(be)
+
+
+@pytest.mark.parametrize("mode,value_dtype,light", [
+    ("signed", np.float64, False), ("special", np.float32, False),            # the whole set: it must reach every bin and every value kernel
+    ("signed", np.float32, True), ("special", np.float64, True), ("cancelling", np.float64, True), ("cancelling", np.float32, True),
+    ("bound", np.float64, True), ("bound", np.float32, True)])
+def test_spgemm_values_exactly(be, capfd, mode, value_dtype, light):
+    """values of C against the long-double sum of the expanded products: `==` on inputs whose partial sums are all representable (signs,
+    cancellation, Inf / NaN / stored zeros, numeric reuse after them), the textbook bound on signed real values; every case proves its kernel.
+    (The emulator adds with a plain atomicAdd: what the hardware's floating-point atomics do is tests/test_gpu_spgemm_values.py's to see.)"""
+    pc.check_spgemm_values(be, capfd, mode, value_dtype, light=light, both_offsets=False)
+
+
+def test_sort_and_merge_sums_exactly(be):
+    pc.check_sort_and_merge_exact(be)
 
 
 def test_spgemm_issue402(be):

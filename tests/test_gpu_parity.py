@@ -799,13 +799,7 @@ def test_spgemm_float_and_laplacian(be):
 
 
 def test_spgemm_all_bins(be):
-    B0 = pc.hub_matrix(64, 30000, 40, {0: 9000, 1: 3000, 2: 600, 3: 120, 5: 20000}, seed=1)
-    rng = np.random.default_rng(2)
-    cols_for = {0: [0], 1: [1], 2: [2], 3: [3, 7], 4: [], 5: [5], 6: [0, 1, 5], 7: list(range(6, 36))}
-    rm = [0]; ent = []
-    for i in range(8):
-        ent += cols_for[i]; rm.append(len(ent))
-    A0 = oracle.Crs(8, 64, np.array(rm), np.array(ent, dtype=np.int32), 1 + 49 * rng.random(len(ent)))
+    A0, B0 = pc.all_bins_operands()
     got = pc.check_spgemm(be, A0, B0)
     sizes = np.diff(got.row_map)
     assert sizes[4] == 0 and sizes[3] <= 256 and 256 < sizes[2] <= 2048 and 2048 < sizes[1] <= 5461 and sizes[0] > 5461
