@@ -199,11 +199,19 @@ int kkamd_spmv_struct(const kkamd_crs_t* A, char mode, int stencil_type, int ndi
  *                       off -- measured equal to the planned stream kernel on C2 --, 1 on; "march_planes" planes per workgroup (20)
  *   kkamd_spmv_struct (global only): "struct_remap", "struct_group", "struct_strip" workgroup orders, all off
  *   "verbose" (global): 1 = the library reports what it chose on stdout
- *   SpGEMM (kkamd_set_default only) "spgemm_win_bits" (columns per LDS bitmap pass), "spgemm_val_cap", "spgemm_val_shape",
- *          "spgemm_val_la", "spgemm_force_unsorted", "spgemm_emit_chunked" (test hooks for alternative code paths);
+ *   SpGEMM (kkamd_set_default only) "spgemm_win_bits" (columns per LDS bitmap pass), "spgemm_emit_win_bits" (the same for the rows that
+ *          walk their products again in the numeric phase; 0 = spgemm_win_bits), "spgemm_val_cap" (entries of C per value window),
+ *          "spgemm_force_unsorted", "spgemm_emit_chunked" (test hooks for alternative code paths);
+ *          "spgemm_val_small_cnt", "spgemm_val_tiny_cnt" (rows of C with at most this many entries take the flat value kernel's 256- / 128-
+ *          work-item shape; 0 = none), "spgemm_block" (1: rows of C that fill "spgemm_block_min_pct" % of the columns -- or
+ *          "spgemm_block_la_pct" % with more than 512 entries in the A row -- take the column-block value kernels; 0: windows only),
+ *          "spgemm_block_w" (columns per block, a power of two up to 16384), "spgemm_items" (1: those rows as items of up to
+ *          "spgemm_item_blocks" blocks and "spgemm_item_cap" entries; 0: one workgroup per row and block),
+ *          "spgemm_keep_bitmaps", "spgemm_keep_lists" (1: the symbolic phase keeps bitmaps / entry lists of its dense rows for the first
+ *          numeric call; 0: those rows walk their products twice), "spgemm_pool_keep" (the process-wide store behind them when the last
+ *          handle goes: 0 returned after the process's first product and kept for repeat users, 1 kept, 2 returned),
  *          "spgemm_emit_sort" (1: entries(C) of rows with more than 256 entries out of at most 2048 products are sorted in LDS, eight rows
- *          per CU; 0: they take the bitmap kernel like every other dense row), "spgemm_col_quads" (0 / 4: 16-byte loads of entries(B) per
- *          work-item and step in the row-by-row bitmap kernels), "spgemm_sym_units" (1, default: the symbolic phase counts its dense class
+ *          per CU; 0: they take the bitmap kernel like every other dense row), "spgemm_sym_units" (1, default: the symbolic phase counts its dense class
  *          by units = (row of C, window of columns), each a workgroup of its own around a 32 KB LDS bitmap, described by heads built from an
  *          index of B and of A's entries at window granularity; 0: one workgroup per row, as before round 6), "spgemm_unit_bits" (log2 of a
  *          unit's window, 6..18, default 18; small values are for tests), "spgemm_store_cap_mb" (upper limit, in MB, of the structure the

@@ -6,23 +6,32 @@
 // team shapes (K12-K14) -> a separate per-row sort pass over C (K17).
 //
 // gfx950-native structure here.  A CU has 160 KB of LDS, so every per-row working set (hash table, column bitmap,
-// value window) lives in LDS and no second level / memory pool exists; HBM holds accumulators only for the few rows of
-// A with more than 4096 entries (or for dense rows when B is not column-sorted):
+// value window) lives in LDS and no second level / memory pool exists; HBM holds accumulators only for the dense rows of
+// a product whose B is not column-sorted (or under SPGEMM_KK_DENSE):
 //   1. spgemm_flops_kernel      upper bound per row, total multiplications, max; rows_sorted_kernel: is B sorted?
 //   2. rows are BINNED by that bound (symbolic) / by their exact nnz (numeric); each bin gets the launch shape
 //      that fits it:
-//      symbolic   flops <= 1365    wave per row, 2048-slot key table (4 rows per workgroup)
-//                 flops <= 2048    256-thread workgroup, 4096-slot table
-//                 flops <= 8192    1024-thread workgroup, 16384-slot table (64 KB: two workgroups per CU)
-//                 above            1024-thread workgroup, k-bit column BITMAP in LDS (2^20 columns per pass), popcount
-//      numeric    nnz <= 256       wave per row, 512-slot key+value table, compaction + rank-by-counting -> sorted
-//                 nnz <= 2048/5461 (only when B is unsorted) workgroup per row, 4096/8192-slot table, bitonic network
-//                 above (dense)    a) the bitmap kernel again, now EMITTING entries(C) in ascending order;
-//                                  b) values: the sorted entries are cut into windows of 2048, each hashed into an LDS
-//                                     table; every A entry keeps a cursor into its (sorted) B row, so a window only
-//                                     streams the part of each B row that falls inside it (dense_vals / hub_vals);
-//                                  c) A rows > 4096 entries or unsorted B: many workgroups per row, L2 atomics into
-//                                     a k-wide HBM accumulator, gathered in C order (hub_acc / hub_extract).
+//      symbolic   flops <= 1365    wave per row, 2048-slot key table (sym_wave; rows of at most kQuadFlops products four per wave: sym_quad)
+//                 flops <= 2048    256-thread workgroup, 4096-slot table (sym_block)
+//                 above (dense)    by UNITS (row, window of 2^18 columns): 256 work-items around a 32 KB column BITMAP in LDS, popcount;
+//                                  a unit's bitmap or entry list is kept for the numeric phase where HBM allows (sym_unit).
+//                                  Fallback (knob sym_units 0, entries(B) not 16-byte aligned, compressed B): one 1024-thread workgroup
+//                                  per row around a k-bit bitmap, 2^20 columns per pass (dense_cols)
+//      numeric    nnz <= 256       wave per row, 512-slot key+value table, compaction + rank-by-counting -> sorted (num_wave / num_quad)
+//                 nnz <= 2048/5461 (only when B is unsorted) workgroup per row, 4096/8192-slot table, bitonic network (num_block)
+//                 above (dense)    a) entries(C) in ascending order: from what the symbolic phase kept (emit_unit; emit_bitmap and
+//                                     copy_pool after the fallback); rows that kept nothing walk their products again -- few products:
+//                                     sorted in LDS (emit_sort), otherwise the bitmap kernel, now EMITTING (dense_cols);
+//                                  b) values, B sorted, by row (numeric_launch_values):
+//                                     rows filling >= 4 % of the columns: column blocks of 16384 with a position-indexed accumulator
+//                                       in LDS, as items (item_vals) or one workgroup per (row, block) (block_vals);
+//                                     A row <= 1024 entries: the sorted entries are cut into windows of 2048, each hashed into an LDS
+//                                       table, the lists (B rows) cut at the window ends by binary search and walked flat (dense_vals2;
+//                                       128, 256 or 512 work-items by the row's entries when the A row has <= 512, 1024 above);
+//                                     longer A rows: the same windows with a cached cursor per list, 4096 lists per pass, one
+//                                       workgroup per (row, pass) (hub_vals);
+//                                  c) values, B unsorted or SPGEMM_KK_DENSE: many workgroups per row, L2 atomics into a k-wide HBM
+//                                     accumulator, gathered in C order (hub_acc / hub_extract).
 //      Block-per-row kernels walk the row's products FLAT (flat_products): a scan of the B row lengths lets work-item q
 //      take product q, so all loads of a lane are independent -- sub-groups chasing "their" B row were bound by the
 //      entries(A) -> row_map(B) -> entries(B) latency chain.
@@ -79,7 +88,7 @@ constexpr int kHashMul   = 107;
 constexpr int kFlopsLong = 512;    // rows of A above this many entries get a workgroup in the row-flops pass
 constexpr int kSymWaveTable = 2048;   // symbolic keys only: 8 KB per wave
 constexpr int kWaveTable = 512;       // numeric keys + values
-constexpr int kSymBlkS = 4096,  kSymBlkL = 16384;   // 64 KB of keys: two workgroups per CU (32768 slots: one; R-MAT s20 symbolic 101 -> 94 ms)
+constexpr int kSymBlkS = 4096;       // symbolic block hash table (16 KB of keys)
 constexpr int kNumBlkS = 4096,  kNumBlkL = 8192;
 constexpr int kDenseBlock = 1024;     // dense-row column kernel: 16 waves around one LDS bitmap
 constexpr int kValBlock   = 512;      // dense-row value kernel
@@ -90,7 +99,6 @@ constexpr int kValTableSmall = 2048;  // ... of the light shape for rows with fe
 constexpr int kValLaSmall = 256;      // ... and its lists per pass (256 work-items)
 constexpr int kValTableTiny = 1024, kValLaTiny = 128;    // the lightest shape: 128 work-items (19 KB of LDS: eight workgroups per CU)
 constexpr int kValLa2     = 1024;     // ... of the flat value kernel's second shape (1024 work-items, one workgroup per CU)
-constexpr int kValLong    = 128;      // B rows at least this long are streamed by a whole wave
 constexpr int kHubLa      = 4096;     // A rows up to this long keep cursor + next column in LDS (hub value kernel)
 
 constexpr int kUnitBitsMaxKnob = 18;  // default of the knob spgemm_unit_bits
@@ -104,15 +112,9 @@ struct SpgemmTuning {
 #ifdef KK_ABLATE
   int debug          = 0;         // measurement build only: ablation bits for the dense-row kernels
 #endif
-  int val_la         = kValLa;    // A rows up to this long use the cached-cursor value kernel (<= kValLa)
-  int val_shape      = 0;         // value-kernel geometry: 0 = 4096 slots x 512 threads (default), 1..4 alternatives
   int emit_win_bits  = 0;         // numeric: bitmap window of the rows whose bitmap was not kept (0 = win_bits)
-  int hub_split      = 1;         // hub rows: one workgroup per pass of kHubLa entries (sums of rows with several passes meet through fp64 atomics)
-  int sym_large      = 0;         // symbolic: rows of 2049..8192 products through the 16384-slot hash kernel; 0 (default) = the bitmap kernel (R-MAT scale 20: the hash kernel spent 21 ms on 137 K such rows, symbolic 78 -> 68 ms without it)
   int keep_bitmaps   = 1;         // symbolic keeps the bitmaps of its densest rows for the first numeric call (0 = every row walks its products twice)
-  int emit_staged    = 1;         // entries(C) of the stored bitmaps leave through wave-private LDS (whole-line stores); 0 = every lane writes its own run
   int keep_lists     = 1;         // ... and the entry lists of the other dense rows, in a pool behind the bitmaps (0 = those rows walk their products twice)
-  int val_la2        = kValLa2;   // ... up to this many entries (above kValLa2: several passes of kValLa2 lists)
   int val_small_cnt  = 65536;     // rows of C with at most this many entries (and at most kValLaSmall entries in the A row) take the flat value kernel's light shape (0 = none;
                                   // R-MAT scale 20 numeric / reuse: 0: 221.7 / 184.7 ms, 8192: 217.6 / 180.7, 32768: 213.8 / 176.6, 65536: 211.1 / 174.6, 131072: 216.4 / 179.5, all: 219.0 / 182.3)
   int val_tiny_cnt   = 32768;     // ... and at most this many (and kValLaTiny entries in the A row) the lightest one: 128 work-items, 1024-slot table (0 = none;
@@ -121,11 +123,6 @@ struct SpgemmTuning {
                                   // kQuadNnz entries (the bin's list is split when it mixes sizes; 7-pt FD 150^3: symbolic 3.54 -> 1.94 ms, numeric 4.24 -> 1.97), 2 = for every row of the
                                   // bin (waves with a larger row do their four rows one after the other: 27-pt FE 100^3 numeric 4.04 -> 5.03 ms, which is why 1 is the default), 0 = never
   int emit_sort      = 1;         // entries(C) of the dense-bin rows with at most kEmitSortCap products: sorted in LDS, 256 work-items per row (0 = the bitmap kernel)
-  int val_mid        = 1;         // A rows of kValLa + 1 .. kValLa2 entries through the flat value kernel's 1024-list shape (0 = the hub kernel)
-  int hub_chunked    = 1;         // A rows above kHubLa entries: 1 = the LDS hub value kernel in passes of kHubLa entries, 0 = L2 atomics into a k-wide HBM accumulator
-  int col_quads      = 4;         // dense-row bitmap kernels read entries(B) as aligned 16-byte quads, 4 or 8 per work-item and step (0 = one 4-byte load per product)
-  int val_hub_flat   = 0;         // 1 = A rows above kValLa through the flat value kernel too (measured slower, see numeric_typed)
-  int val_kernel     = 2;         // dense rows with short A rows: 2 = flat walk with the lists cut per window group (default), 1 = wave-per-list streaming
   int block          = 1;         // rows of C that are dense (or have more lists than the flat kernel's shapes) through the column-block value kernel (0 = windows only)
   int block_w        = 16384;     // its columns per block (a power of two; 16384 = 128 KB of fp64 sums)
   int items          = 1;         // the column-block class as ITEMS (groups of blocks with a position-indexed accumulator, dense blocks direct); 0 = one workgroup per (row, block)
@@ -133,9 +130,6 @@ struct SpgemmTuning {
   int item_cap       = 6144;      // entries of C per rank item (48 KB of sums; with the 16 KB of packed words two workgroups per CU)
   int block_min_pct  = 4;         // ... rows with at least this percentage of the columns (R-MAT scale 20 reuse, items: 20 %: 109.0 ms, 9 %: 101.1, 6 %: 98.1, 4 %: 96.7, 3 %: 96.7, 2 %: 99.4, 1 %: 107.7; one workgroup per (row, block): 6 %: 136.5, 12 %: 117.1, 20 %: 115.9) ...
   int block_la_pct   = 3;         // ... or at least this percentage and more than kValLa lists
-  int list_staged    = 1;         // symbolic: the entry lists kept for the numeric phase are written wave by wave, 64 consecutive words per round (0 = every lane writes its own run)
-  int nt             = 0;         // value kernels of the dense rows: entries(C) / values(C) through nontemporal loads / stores
-  int sort_rows      = 1;         // the row lists of the dense kernels are ordered by size, largest first (0 = the order the binning left)
   int sym_units      = 1;         // symbolic phase of the dense class by units (row, window of 2^unit_bits columns): spgemm_sym_unit_kernel; 0 = one workgroup per row (spgemm_dense_cols_kernel)
   int unit_bits      = kUnitBitsMaxKnob;   // log2 of a unit's columns (6 .. 18; 18 = 32 KB of bitmap, four workgroups of 256 per CU)
   int store_cap_mb   = 0;         // upper bound, in MB, on the store of kept structure (bitmaps / entry lists of the symbolic phase) a product may take; 0 = none beyond the
@@ -146,8 +140,8 @@ struct SpgemmTuning {
 static SpgemmTuning g_spgemm;
 
 struct BinLimits { int64_t lim[kNumBins - 1]; };   // size <= lim[b] -> bin b  (lim[0] = 0)
-static const BinLimits kSymLimits = {{0, (kSymWaveTable * 2) / 3, kSymBlkS / 2, kSymBlkL / 2}};
-static const BinLimits kSymLimitsNoLarge = {{0, (kSymWaveTable * 2) / 3, kSymBlkS / 2, kSymBlkS / 2}};   // knob sym_large 0: rows above 2048 products straight to the bitmap kernel
+// (no third bin: rows above 2048 products go straight to the bitmap kernels -- a 16384-slot hash kernel spent 21 ms on R-MAT scale 20's 137 K rows of 2049..8192 products)
+static const BinLimits kSymLimits = {{0, (kSymWaveTable * 2) / 3, kSymBlkS / 2, kSymBlkS / 2}};
 static const BinLimits kSymLimitsC = {{0, (1024 * 2) / 3, 4096 / 2, 16384 / 2}};     // compressed symbolic (keys + masks: smaller tables)
 static const BinLimits kAllDense = {{0, 0, 0, 0}};                                   // every non-empty row in the last bin
 static const BinLimits kNumLimits = {{0, kWaveTable / 2, kNumBlkS / 2, (kNumBlkL * 2) / 3}};
@@ -285,14 +279,7 @@ __global__ __launch_bounds__(kBlock) void rows_sorted_long_kernel(int64_t n, con
   }
   if (bad) *unsorted = 1;
 }
-// sum of the per-row counts (before the scan) in 64 bits: a 32-bit row_map must not wrap silently
-template <class OffT> __global__ void sum_counts_kernel(int64_t m, const OffT* __restrict__ counts, unsigned long long* out) {
-  unsigned long long s = 0;
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (int64_t)gridDim.x * blockDim.x) s += (unsigned long long)counts[r];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
-}
-// ... and with the largest count (the reference's set_max_result_nnz, impl_symbolic.hpp:1501-1505): out[0] += sum, out[1] = max
+// sum of the per-row counts (before the scan) in 64 bits -- a 32-bit row_map must not wrap silently -- and the largest count (the reference's set_max_result_nnz, impl_symbolic.hpp:1501-1505): out[0] += sum, out[1] = max
 template <class OffT> __global__ void sum_max_counts_kernel(int64_t m, const OffT* __restrict__ counts, unsigned long long* out) {
   unsigned long long s = 0, mx = 0;
   for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (int64_t)gridDim.x * blockDim.x) {
@@ -400,31 +387,12 @@ template <int H> __device__ __forceinline__ int vt_find(const int* hk, int key) 
 // share an A entry and stride over that B row.  s is at least sg_log2 (the matrix-wide hint: average B row length) and
 // grows for rows of A with few entries so that the sub-groups (nthreads >> s of them) just cover the row -- a row with
 // 13 entries handled by 1024 work-items runs 16 sub-groups of 64 lanes instead of leaving 115 of 128 idle.
-// Each lane issues kProdUnroll independent B loads per step (a step is latency-bound otherwise): f(a, j, column).
+// Each lane issues kProdUnroll independent B loads per step (a step is latency-bound otherwise), the B value alongside the column:
+// f(a, column, value of B).
 #ifndef KK_PROD_UNROLL
 #define KK_PROD_UNROLL 4
 #endif
 constexpr int kProdUnroll = KK_PROD_UNROLL;
-template <class OffT, class F>
-__device__ __forceinline__ void for_each_product(int64_t row, const OffT* __restrict__ rmA, const int32_t* __restrict__ entA,
-                                                 const OffT* __restrict__ rmB, const int32_t* __restrict__ entB, int tid,
-                                                 int nthreads, int sg_log2, F f) {
-  const int64_t a_beg = (int64_t)rmA[row], a_end = (int64_t)rmA[row + 1];
-  while ((int64_t)(nthreads >> (sg_log2 + 1)) >= a_end - a_beg && (2 << sg_log2) <= nthreads) ++sg_log2;
-  const int sg = 1 << sg_log2, sub = tid >> sg_log2, nsub = nthreads >> sg_log2, sl = tid & (sg - 1);
-  for (int64_t a = a_beg + sub; a < a_end; a += nsub) {
-    const int32_t c    = entA[a];
-    const int64_t b_end = (int64_t)rmB[c + 1];
-    for (int64_t j = (int64_t)rmB[c] + sl; j < b_end; j += (int64_t)sg * kProdUnroll) {
-      int col[kProdUnroll];
-      KK_UNROLL
-      for (int u = 0; u < kProdUnroll; ++u) { const int64_t ju = j + (int64_t)u * sg; col[u] = ju < b_end ? entB[ju] : -1; }
-      KK_UNROLL
-      for (int u = 0; u < kProdUnroll; ++u) if (col[u] >= 0) f(a, j + (int64_t)u * sg, col[u]);
-    }
-  }
-}
-// same with the B value loaded alongside the column: f(a, column, value of B)
 template <class OffT, class VT, class F>
 __device__ __forceinline__ void for_each_product_v(int64_t row, const OffT* __restrict__ rmA, const int32_t* __restrict__ entA,
                                                    const OffT* __restrict__ rmB, const int32_t* __restrict__ entB,
@@ -1021,47 +989,13 @@ __global__ __launch_bounds__(NT) void spgemm_sym_block_kernel(int64_t nbin, cons
 typedef unsigned long long kk_u64;
 // The set bits of bm[0 .. words) (LDS or HBM), as columns col0 + bit index in ascending order, to entC[pos0 ...]; returns their number.
 // Every wave owns a contiguous range of the words and walks it 64 words at a time (lane l owns word base + l): the loads of a wave
-// are 512 contiguous bytes, neighbouring lanes write neighbouring pieces of entries(C), the offsets inside a wave come from shuffles
-// and only the 16 wave totals cross the workgroup (one barrier).  (One contiguous run of words per work-item made every store of a
-// wave 64 separate short runs: 4-byte stores into 64 different sectors; 1024 interleaved words per step cost sixteen workgroup scans
-// per row.)  words <= 16384 (2^20 columns).  All kDenseBlock work-items call it; s_wave must be free (a barrier since its last use).
-__device__ __forceinline__ int emit_bits_by_wave(const kk_u64* __restrict__ bm, int words, int64_t col0, int64_t pos0, int32_t* __restrict__ entC, int* s_wave) {
-  constexpr int NW = kDenseBlock / 64, NB = 16;            // 2^20 columns / 64 / 1024 = 16 steps of 64 words per wave
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int wpw = ((words + NW - 1) / NW + 63) & ~63;       // words per wave, a multiple of 64
-  const int w0 = wave * wpw, w1 = (w0 + wpw < words) ? w0 + wpw : words;
-  kk_u64 w[NB];
-  int wsum = 0;
-  KK_UNROLL
-  for (int i = 0; i < NB; ++i) { const int wd = w0 + i * 64 + lane; w[i] = (i * 64 < wpw && wd < w1) ? bm[wd] : 0ull; wsum += __popcll(w[i]); }
-  for (int o = 32; o > 0; o >>= 1) wsum += __shfl_xor(wsum, o, 64);
-  if (lane == 0) s_wave[wave] = wsum;
-  __syncthreads();
-  int tot = 0;
-  for (int i = 0; i < NW; ++i) { if (i == wave) pos0 += tot; tot += s_wave[i]; }
-  KK_UNROLL
-  for (int i = 0; i < NB; ++i) {
-    if (i * 64 >= wpw) break;                              // uniform
-    kk_u64 v = w[i];
-    const int pc = __popcll(v);
-    int inc = pc;
-    for (int o = 1; o < 64; o <<= 1) { const int nb_ = __shfl_up(inc, (unsigned)o, 64); if (lane >= o) inc += nb_; }
-    int64_t pos = pos0 + (inc - pc);
-    const int64_t c0 = col0 + (int64_t)(w0 + i * 64 + lane) * 64;
-    while (v) {
-      const int bit = __ffsll(v) - 1;
-      entC[pos++]   = (int32_t)(c0 + bit);
-      v &= v - 1;
-    }
-    pos0 += __shfl(inc, 63, 64);
-  }
-  return tot;
-}
-// The same through wave-private LDS: a wave's 64 words are taken 16 at a time -- lane l owns the l-th 16-bit piece of the 16 words, so
+// are 512 contiguous bytes, the offsets inside a wave come from shuffles and only the wave totals cross the workgroup (one barrier).
+// words <= 1024 NT / 64 (2^20 columns for 1024 work-items).  All NT work-items call it; s_wave must be free (a barrier since its last use).
+// The entries leave through wave-private LDS: a wave's 64 words are taken 16 at a time -- lane l owns the l-th 16-bit piece of the 16 words, so
 // the pieces ascend with the lanes --, the pieces' columns are laid down in order in 4 KB of LDS, and the (at most 1024) entries leave
-// with store instructions whose 64 lanes write 64 CONSECUTIVE entries.  With the direct form every lane writes its own run of up to
-// 64 entries, i.e. every store instruction is 64 four-byte pieces in 64 different lines: on R-MAT scale 20 the stored bitmaps emit
-// 8e9 entries = 8e9 L2 write requests in 27.9 ms -- the L2's request rate, not its bandwidth (32 GB at 1.15 TB/s).
+// with store instructions whose 64 lanes write 64 CONSECUTIVE entries.  (Every lane writing its own run of up to 64 entries
+// straight to entries(C) made every store instruction 64 four-byte pieces in 64 different lines: on R-MAT scale 20 the stored bitmaps
+// emitted 8e9 entries = 8e9 L2 write requests in 27.9 ms -- the L2's request rate, not its bandwidth (32 GB at 1.15 TB/s).)
 // (Measured and not kept: every lane laying down the set bits of its OWN 64-bit word -- no shuffles at all, one prefix sum per 64 words,
 // steps above 1024 entries taken in halves or quarters of the lanes: R-MAT scale 20 numeric 193.7 -> 200.9 ms; the 16-bit pieces below
 // keep the divergent loop at 16 trips at most.)
@@ -1208,7 +1142,6 @@ struct BitmapStore {                 // where the symbolic count kernel may leav
   long long* pool_off = nullptr;     // [m], -1 = not written
   unsigned long long* pool_cursor = nullptr;
   long long pool_cap = 0;
-  int list_staged = 1;               // the lists are written wave by wave, 64 consecutive words per round (0 = every lane its own run of words)
 };
 template <class OffT, bool EMIT, int Q = 4>
 __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const int32_t* __restrict__ perm,
@@ -1229,7 +1162,7 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const in
   const int t       = threadIdx.x;
   const int64_t row = perm[blockIdx.x];
   int64_t total     = 0;
-  int ch_a = 0, ch_z = 0, ch_excl = 0, ch_per = 0;                 // (count only) the work-item's run of words in the last window, its offset and the words per work-item
+  int ch_a = 0, ch_excl = 0, ch_per = 0;                           // (count only) the first word of the work-item's run in the last window, its offset and the words per work-item
   (void)sg_log2;
   for (int64_t c0 = 0; c0 < k; c0 += win_bits) {
     const int nbits  = (int)((k - c0 < (int64_t)win_bits) ? k - c0 : (int64_t)win_bits);
@@ -1269,7 +1202,7 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const in
       // sparse bitmaps (fewer than 4 columns per touched word on average; always when only counting): every
       // work-item takes one contiguous run of words -- one workgroup scan per window instead of one per 1024 words.
       // Dense bitmaps keep the interleaved walk, whose stores to entries(C) coalesce.  (The wave-contiguous walk of
-      // emit_bits_by_wave, which serves the stored bitmaps, measured slower here on the sparse rows: R-MAT scale 20 numeric 261 -> 271 ms.)
+      // emit_bits_by_wave_staged, which serves the stored bitmaps, measured slower here on the sparse rows: R-MAT scale 20 numeric 261 -> 271 ms.)
       const bool chunked = !EMIT || force_chunked || (int64_t)rmC[row + 1] - (int64_t)rmC[row] < 4 * (int64_t)nw;
       if (chunked) {
         const int per = (nw + kDenseBlock - 1) / kDenseBlock;
@@ -1278,7 +1211,7 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const in
         for (int wd = a; wd < z; ++wd) cnt += __popcll(bm[wd]);
         int tot;
         const int excl = block_exclusive_scan_n<int, kDenseBlock>(cnt, &tot, s_wave);
-        ch_a = a; ch_z = z; ch_excl = excl; ch_per = per;
+        ch_a = a; ch_excl = excl; ch_per = per;
         if (EMIT && !KK_DBG(1)) {
           int64_t pos = (int64_t)rmC[row] + total + excl;
           for (int wd = a; wd < z; ++wd) {
@@ -1341,39 +1274,31 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const in
       if (poff >= 0) {
         // (staging the list in LDS -- the product walk's scratch -- and writing it out in whole lines, 6144 entries per round, measured
         // slower: dense_cols<false> 70 -> 115 ms on R-MAT scale 20.  Each work-item writes the entries of its run of words where they stand.)
-        if (bs.list_staged) {
-          // The count gave every work-item a contiguous run of `per` words, so a WAVE holds 64 per consecutive words and its entries
-          // start at the offset of its first lane.  For the emission the wave takes them 64 at a time -- lane l the l-th word of the
-          // round: consecutive LDS words (no bank conflict), a prefix sum of the popcounts on the vector unit, and the lanes' entries
-          // of a round follow each other in the list: on the sparse bitmaps these rows have (one or two bits per word) the 64 lanes of
-          // a store instruction write one or two lines.  (Every lane writing the entries of its own run of `per` words: 64 different
-          // lines per store instruction, 17 of the symbolic phase's 62 ms on R-MAT scale 20.  Passing the wave's entries through a small
-          // wave-private LDS buffer instead serialises the lanes of a wave whose words are dense: 60 -> 232 ms.)
-          const int lane = t & 63;
-          const int per = ch_per;
-          const int wave_w0 = wave_first_lane_i32(ch_a);               // first word of the wave (the runs ascend with the lanes)
-          const int w_end = s_max >> 6;                                // last touched word of the row
-          int run = wave_first_lane_i32(ch_excl);
-          int32_t* dst = bs.pool + poff;
-          for (int i = 0; i < per; ++i) {                              // (uniform)
-            const int wd = wave_w0 + i * 64 + lane;
-            kk_u64 v = wd <= w_end ? bm[wd] : 0ull;
-            const int pc = __popcll(v);
-            const int inc = wave_inclusive_scan_i32(pc, lane);
-            int pos = run + inc - pc;
-            // the two 32-bit halves one after the other: five vector instructions per bit instead of twelve for the 64-bit find-first / clear
-            unsigned lo32 = (unsigned)v, hi32 = (unsigned)(v >> 32);
-            const int cbase = wd * 64;
-            while (lo32) { dst[pos++] = cbase + (__ffs((int)lo32) - 1); lo32 &= lo32 - 1u; }
-            while (hi32) { dst[pos++] = cbase + 32 + (__ffs((int)hi32) - 1); hi32 &= hi32 - 1u; }
-            run += wave_last_lane_i32(inc);
-          }
-        } else {
-          int32_t* dst = bs.pool + poff + ch_excl;
-          for (int wd = ch_a; wd < ch_z; ++wd) {
-            kk_u64 v = bm[wd];
-            while (v) { const int bit = __ffsll(v) - 1; *dst++ = (int32_t)((int64_t)wd * 64 + bit); v &= v - 1; }
-          }
+        // The count gave every work-item a contiguous run of `per` words, so a WAVE holds 64 per consecutive words and its entries
+        // start at the offset of its first lane.  For the emission the wave takes them 64 at a time -- lane l the l-th word of the
+        // round: consecutive LDS words (no bank conflict), a prefix sum of the popcounts on the vector unit, and the lanes' entries
+        // of a round follow each other in the list: on the sparse bitmaps these rows have (one or two bits per word) the 64 lanes of
+        // a store instruction write one or two lines.  (Every lane writing the entries of its own run of `per` words: 64 different
+        // lines per store instruction, 17 of the symbolic phase's 62 ms on R-MAT scale 20.  Passing the wave's entries through a small
+        // wave-private LDS buffer instead serialises the lanes of a wave whose words are dense: 60 -> 232 ms.)
+        const int lane = t & 63;
+        const int per = ch_per;
+        const int wave_w0 = wave_first_lane_i32(ch_a);               // first word of the wave (the runs ascend with the lanes)
+        const int w_end = s_max >> 6;                                // last touched word of the row
+        int run = wave_first_lane_i32(ch_excl);
+        int32_t* dst = bs.pool + poff;
+        for (int i = 0; i < per; ++i) {                              // (uniform)
+          const int wd = wave_w0 + i * 64 + lane;
+          kk_u64 v = wd <= w_end ? bm[wd] : 0ull;
+          const int pc = __popcll(v);
+          const int inc = wave_inclusive_scan_i32(pc, lane);
+          int pos = run + inc - pc;
+          // the two 32-bit halves one after the other: five vector instructions per bit instead of twelve for the 64-bit find-first / clear
+          unsigned lo32 = (unsigned)v, hi32 = (unsigned)(v >> 32);
+          const int cbase = wd * 64;
+          while (lo32) { dst[pos++] = cbase + (__ffs((int)lo32) - 1); lo32 &= lo32 - 1u; }
+          while (hi32) { dst[pos++] = cbase + 32 + (__ffs((int)hi32) - 1); hi32 &= hi32 - 1u; }
+          run += wave_last_lane_i32(inc);
         }
         if (t == 0) bs.pool_off[row] = poff;
       }
@@ -1385,12 +1310,11 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_dense_cols_kernel(const in
 template <class OffT>
 __global__ __launch_bounds__(kDenseBlock) void spgemm_emit_bitmap_kernel(const int32_t* __restrict__ perm, const int32_t* __restrict__ row_slot,
                                                                          const kk_u64* __restrict__ store, int words, const OffT* __restrict__ rmC,
-                                                                         int32_t* __restrict__ entC, int staged) {
+                                                                         int32_t* __restrict__ entC) {
   __shared__ int s_wave[kDenseBlock / 64];
   __shared__ int32_t s_stage[kDenseBlock / 64][1024];
   const int64_t row = perm[blockIdx.x];
-  if (staged) (void)emit_bits_by_wave_staged(store + (size_t)row_slot[row] * (size_t)words, words, 0, (int64_t)rmC[row], entC, s_wave, s_stage[threadIdx.x >> 6]);
-  else (void)emit_bits_by_wave(store + (size_t)row_slot[row] * (size_t)words, words, 0, (int64_t)rmC[row], entC, s_wave);
+  (void)emit_bits_by_wave_staged(store + (size_t)row_slot[row] * (size_t)words, words, 0, (int64_t)rmC[row], entC, s_wave, s_stage[threadIdx.x >> 6]);
 }
 // rows of a bin whose size (products) reaches thr -> count[0]; count[1] = a bound on the ENTRIES of all rows of the bin (a row has at
 // most as many entries as products, and at most kcols): what the entry lists kept for the numeric phase can need at most
@@ -1443,7 +1367,6 @@ __global__ __launch_bounds__(kBlock) void spgemm_copy_pool_kernel(const int32_t*
 #ifndef KK_UQ
 #define KK_UQ 4
 #endif
-constexpr int kUnitNT = 256;
 constexpr int kUnitBitsMax = 18;                                              // 2^18 columns = 32 KB of bitmap for 256 work-items: four workgroups per CU
 // (Measured and not kept: windows of 2^19 / 2^20 columns around workgroups of 512 / 1024 -- R-MAT scale 20 symbolic 39.1 / 48.7 ms against 40.0, scale 18 6.2 / 8.0
 // against 5.4; the template takes the workgroup size, only 256 is instantiated.)
@@ -2336,192 +2259,17 @@ __global__ __launch_bounds__(kBlock) void spgemm_split_block_kernel(int64_t nd, 
   }
 }
 
-// dense rows, values (B rows column-sorted, at most kValLa entries in the A row): entries(C) of the row are already
-// in place and sorted (spgemm_dense_cols_kernel<EMIT>), so the row is cut into windows of `cap` consecutive C entries.
-// A window's columns are hashed into a clean LDS table (each work-item keeps the slots of its columns in registers).
-// The resume point of every A entry (position in B, entries left, A value) lives in LDS, so every B entry is consumed
-// exactly once although the row is visited window by window:
-//   * B rows of >= kValLong entries: one wave per A entry, two entries in flight, 128 consecutive B entries per step;
-//   * shorter B rows: sub-groups of 8..64 lanes (fewer A entries -> wider groups) that each own one A entry at a time
-//     and move on when it has nothing left inside the window -- up to 8 independent B streams per wave.
-// Columns are probed (known to be present) and accumulated with ds_add.  The sums leave in C order, coalesced, and
-// every work-item clears its slots so the table is clean for the next window; the next window's columns are already
-// in flight while the current one streams.
-template <class OffT, class VT, int H, int NT>
-__global__ __launch_bounds__(NT) void spgemm_dense_vals_kernel(const int32_t* __restrict__ perm,
-                                                                      const OffT* __restrict__ rmA, const int32_t* __restrict__ entA,
-                                                                      const VT* __restrict__ valA, const OffT* __restrict__ rmB,
-                                                                      const int32_t* __restrict__ entB, const VT* __restrict__ valB,
-                                                                      const OffT* __restrict__ rmC, const int32_t* __restrict__ entC,
-                                                                      VT* __restrict__ valC, int cap KK_DBG_PARAM) {
-  __shared__ int hk[H];
-  __shared__ VT hv[H];
-  __shared__ long long s_cur[kValLa];
-  __shared__ int s_rem[kValLa];
-  __shared__ VT s_av[kValLa];
-  __shared__ unsigned char s_long[kValLa];
-  __shared__ int s_whi;
-  constexpr int UL = 2, US = 2;       // independent B loads per lane and step (long / short B rows)
-  constexpr int EL = 4;               // long B rows in flight per wave
-  constexpr int KPT = (H / 2 + NT - 1) / NT;   // C entries of a window per work-item
-  constexpr int NW  = NT / 64;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int64_t row = perm[blockIdx.x];
-  const int64_t a0 = (int64_t)rmA[row], la = (int64_t)rmA[row + 1] - a0;
-  const int64_t la_c = la < kValLa ? la : kValLa;
-  const int64_t base = (int64_t)rmC[row], cnt = (int64_t)rmC[row + 1] - base;
-  int sg_log2 = 3;
-  while ((int64_t)(NT >> (sg_log2 + 1)) >= la && sg_log2 < 6) ++sg_log2;
-  const int sg = 1 << sg_log2, sub = t >> sg_log2, nsub = NT >> sg_log2, sl = t & (sg - 1);
-  const int sg_shift   = lane & ~(sg - 1);
-  const kk_u64 sg_mask = sg == 64 ? ~0ull : ((1ull << sg) - 1ull);
-  // A B row is streamed by a whole wave (UL * 64 entries per step) only when a window is expected to take about a wave's worth
-  // of it: the row's entries spread over cnt / cap windows, so len * cap / cnt of them fall into one.  (With the fixed
-  // threshold kValLong every window re-read 128 entries of every hub row to consume a handful: 17 of the 23.7 ms of this
-  // kernel on R-MAT scale 18 were spent there.)
-  const int64_t long_est = 64 * cnt / (cap > 0 ? cap : 1);
-  const int long_min = (int)(long_est > kValLong ? (long_est < INT_MAX ? long_est : INT_MAX) : kValLong);
-  for (int64_t a = t; a < la_c; a += NT) {
-    const int32_t kc = entA[a0 + a];
-    const int64_t b0 = (int64_t)rmB[kc];
-    const int len    = (int)((int64_t)rmB[kc + 1] - b0);
-    s_cur[a] = b0; s_rem[a] = len; s_av[a] = valA[a0 + a]; s_long[a] = len >= long_min ? 1 : 0;
-  }
-  for (int i = t; i < H; i += NT) { hk[i] = -1; hv[i] = VT(0); }
-  auto accumulate = [&](int c, VT v) {
-    const int hh = vt_find<H>(hk, c);
-    if (hh >= 0) KK_ATOMIC_FADD(&hv[hh], v);
-  };
-  // one streaming step of a long B row by a whole wave: UL * 64 consecutive entries, columns and values loaded together
-  auto load_step = [&](int64_t p, int rem, int* c, VT* v) {
-    KK_UNROLL
-    for (int u = 0; u < UL; ++u) {
-      const int idx = u * 64 + lane;
-      const bool ok = idx < rem && !KK_DBG(1024);
-      c[u] = ok ? entB[p + idx] : INT_MAX;
-      v[u] = ok ? valB[p + idx] : VT(0);
-    }
-  };
-  auto consume_step = [&](const int* c, const VT* v, VT av, int whi) -> int {
-    int nin = 0;
-    KK_UNROLL
-    for (int u = 0; u < UL; ++u) {
-      const bool in = c[u] <= whi;
-      if (in && !KK_DBG(512)) accumulate(c[u], av * v[u]);
-      nin += __popcll(__ballot(in));
-    }
-    return nin;
-  };
-  int curk[KPT], slot[KPT];
-  KK_UNROLL
-  for (int q = 0; q < KPT; ++q) { const int i = t + q * NT; curk[q] = (i < cap && i < cnt) ? entC[base + i] : -1; }
-  __syncthreads();
-  for (int64_t done = 0; done < cnt; done += cap) {
-    const int n = (int)(cnt - done < (int64_t)cap ? cnt - done : (int64_t)cap);
-    // build: this window's columns into the (clean) table; the slot of every column stays in a register for the end
-    KK_UNROLL
-    for (int q = 0; q < KPT; ++q) {
-      slot[q] = -1;
-      if (curk[q] >= 0) {
-        slot[q] = vt_insert<H>(hk, curk[q]);
-        if (t + q * NT == n - 1) s_whi = curk[q];
-      }
-    }
-    int nxtk[KPT];        // next window's columns: in flight while this window streams
-    KK_UNROLL
-    for (int q = 0; q < KPT; ++q) {
-      const int i = t + q * NT;
-      nxtk[q]     = (i < cap && done + cap + i < cnt) ? entC[base + done + cap + i] : -1;
-    }
-    __syncthreads();
-    const int whi    = s_whi;
-    const bool last = done + n >= cnt;
-    // long B rows: one wave per A entry, EL entries in flight per wave
-    if (!KK_DBG(32)) for (int64_t a = wave; a < la_c; a += EL * NW) {
-      bool ok[EL];
-      int64_t p[EL];
-      int rem[EL];
-      VT av[EL];
-      int c[EL][UL];
-      VT v[EL][UL];
-      KK_UNROLL
-      for (int e = 0; e < EL; ++e) {
-        const int64_t ae = a + e * NW;
-        ok[e] = ae < la_c && s_long[ae] != 0;
-        if (ok[e]) { p[e] = s_cur[ae]; rem[e] = s_rem[ae]; av[e] = s_av[ae]; load_step(p[e], rem[e], c[e], v[e]); }
-      }
-      KK_UNROLL
-      for (int e = 0; e < EL; ++e) {
-        if (!ok[e]) continue;
-        int nin = consume_step(c[e], v[e], av[e], whi);
-        p[e] += nin; rem[e] -= nin;
-        while (nin == UL * 64) { load_step(p[e], rem[e], c[e], v[e]); nin = consume_step(c[e], v[e], av[e], whi); p[e] += nin; rem[e] -= nin; }
-        if (!last && lane == 0) { s_cur[a + e * NW] = p[e]; s_rem[a + e * NW] = rem[e]; }
-      }
-    }
-    // short B rows: persistent sub-groups
-    int64_t a = sub, p = 0;
-    int rem = 0;
-    VT av   = VT(0);
-    bool have = false;
-    auto fetch = [&]() {
-      while (a < la_c && s_long[a]) a += nsub;
-      have = a < la_c;
-      if (have) { p = s_cur[a]; rem = s_rem[a]; av = s_av[a]; }
-    };
-    fetch();
-    if (KK_DBG(64)) have = false;
-    while (true) {
-      int c[US];
-      VT v[US];
-      KK_UNROLL
-      for (int u = 0; u < US; ++u) {
-        const int idx = u * sg + sl;
-        const bool ok = have && idx < rem;
-        c[u] = ok ? entB[p + idx] : INT_MAX;
-        v[u] = ok ? valB[p + idx] : VT(0);
-      }
-      int nin = 0;
-      KK_UNROLL
-      for (int u = 0; u < US; ++u) {
-        const bool in = c[u] <= whi;
-        if (in) accumulate(c[u], av * v[u]);
-        nin += __popcll((__ballot(in) >> sg_shift) & sg_mask);
-      }
-      if (have) {
-        p += nin; rem -= nin;
-        if (nin < US * sg) {       // this A entry has nothing more inside the window: park it, take the next one
-          if (!last && sl == 0) { s_cur[a] = p; s_rem[a] = rem; }
-          a += nsub;
-          fetch();
-        }
-      }
-      if (__ballot(have) == 0ull) break;
-    }
-    __syncthreads();
-    // sums leave in C order (coalesced); every work-item cleans the slots it filled, so the table is clean again
-    KK_UNROLL
-    for (int q = 0; q < KPT; ++q) {
-      if (slot[q] >= 0) {
-        valC[base + done + t + q * NT] = hv[slot[q]];
-        hk[slot[q]] = -1; hv[slot[q]] = VT(0);
-      }
-      curk[q] = nxtk[q];
-    }
-    __syncthreads();
-  }
-}
-
-// dense rows, values, second form (default; B rows column-sorted, at most kValLa entries in the A row): the same windows of
-// `cap` consecutive C entries hashed into a clean LDS table, but the B side is walked FLAT.  Every list (one per A entry: a
+// dense rows, values (B rows column-sorted, at most kValLa2 entries in the A row): entries(C) of the row are already in place and
+// sorted, so the row is cut into windows of `cap` consecutive C entries, each hashed into a clean LDS table (every work-item keeps
+// the slots of its columns in registers), and the B side is walked FLAT.  Every list (one per A entry: a
 // sorted B row scaled by the A value) is cut at the upper column of each of the next G windows by a binary search -- G * la
 // independent searches spread over the workgroup, once per group of G windows, instead of every wave discovering the end of
 // "its" list by streaming 128 entries at a time.  With the cuts known a window is: one scan of the lists' in-window counts,
 // then product q goes to work-item q / U (U neighbouring products per work-item, all loads independent, nothing read that is
-// not consumed), the hash is probed for a column known to be present, ds_add.  The first form (spgemm_dense_vals_kernel) gave
+// not consumed), the hash is probed for a column known to be present, ds_add.  (An earlier form, wave-per-list streaming, gave
 // the long lists of a window to one wave each: on R-MAT three of a row's sixteen lists carry the products, so one to three
 // waves of eight worked through sequential 128-entry round trips while the others sat at the barrier (R-MAT scale 20:
-// 158 ms for 1.4e10 products, VALU busy 6 %).  LA = lists per pass (A rows above LA take several passes): 512 with 512 work-items
+// 158 ms for 1.4e10 products, VALU busy 6 %.)  LA = lists per pass (A rows above LA take several passes): 512 with 512 work-items
 // (78 KB of LDS: two workgroups per CU), 1024 with 1024 work-items and groups of four windows (88 KB: one per CU) for A rows of
 // 513..1024 entries, which the cached-cursor hub kernel below serves at half the rate per product (every window re-fetches the
 // cache lines of ~5 useful entries per list: 7x read amplification).
@@ -2534,11 +2282,9 @@ __global__ __launch_bounds__(NT) void spgemm_dense_vals2_kernel(const int32_t* _
                                                                        const VT* __restrict__ valA, const OffT* __restrict__ rmB,
                                                                        const int32_t* __restrict__ entB, const VT* __restrict__ valB,
                                                                        const OffT* __restrict__ rmC, const int32_t* __restrict__ entC,
-                                                                       VT* __restrict__ valC, int cap_nt, int64_t nnzB KK_DBG_PARAM) {
+                                                                       VT* __restrict__ valC, int cap_arg, int64_t nnzB KK_DBG_PARAM) {
   static_assert(NT >= LA, "one work-item per list in the scan");
-  // bit 30 of the argument: entries(C) / values(C) -- read once, written once -- go through nontemporal loads and stores, so that they do not
-  // push the rows of B out of the caches on their way (knob spgemm_nt)
-  const int cap = cap_nt & 0xFFFFFF; const bool nt = (cap_nt >> 30) & 1;
+  const int cap = cap_arg & 0xFFFFFF;      // cap <= H / 2; the mask lets the compiler see a 24-bit value (without it: two to four more spilled SGPRs per shape)
   __shared__ int hk[H];
   __shared__ VT hv[H];
   __shared__ long long s_cur[LA];     // first unconsumed entry of list a (index into entries / values of B)
@@ -2574,7 +2320,7 @@ __global__ __launch_bounds__(NT) void spgemm_dense_vals2_kernel(const int32_t* _
     }
     int curk[KPT], slot[KPT];
     KK_UNROLL
-    for (int q = 0; q < KPT; ++q) { const int i = t + q * NT; curk[q] = (i < cap && i < cnt) ? (nt ? KK_NT_LOAD(entC + base + i) : entC[base + i]) : -1; }
+    for (int q = 0; q < KPT; ++q) { const int i = t + q * NT; curk[q] = (i < cap && i < cnt) ? entC[base + i] : -1; }
     __syncthreads();
     for (int64_t gdone = 0; gdone < cnt; gdone += (int64_t)G * cap) {
       const int ng = (int)((cnt - gdone + cap - 1) / cap < G ? (cnt - gdone + cap - 1) / cap : G);     // windows in this group
@@ -2608,7 +2354,7 @@ __global__ __launch_bounds__(NT) void spgemm_dense_vals2_kernel(const int32_t* _
         KK_UNROLL
         for (int q = 0; q < KPT; ++q) {
           const int i = t + q * NT;
-          nxtk[q]     = (i < cap && done + cap + i < cnt) ? (nt ? KK_NT_LOAD(entC + base + done + cap + i) : entC[base + done + cap + i]) : -1;
+          nxtk[q]     = (i < cap && done + cap + i < cnt) ? entC[base + done + cap + i] : -1;
         }
         // in-window counts of the lists -> product offsets
         const int from = (t < la_c && g > 0) ? s_pos[g - 1][t] : 0;
@@ -2719,7 +2465,7 @@ __global__ __launch_bounds__(NT) void spgemm_dense_vals2_kernel(const int32_t* _
           if (slot[q] >= 0) {
             VT* out = valC + base + done + t + q * NT;
             const VT sum = first_pass ? hv[slot[q]] : *out + hv[slot[q]];
-            if (nt) KK_NT_STORE(out, sum); else *out = sum;
+            *out = sum;
             hk[slot[q]] = -1; hv[slot[q]] = VT(0);
           }
           curk[q] = nxtk[q];
@@ -2755,8 +2501,8 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_hub_vals_kernel(const int3
                                                                       const VT* __restrict__ valA, const OffT* __restrict__ rmB,
                                                                       const int32_t* __restrict__ entB, const VT* __restrict__ valB,
                                                                       const OffT* __restrict__ rmC, const int32_t* __restrict__ entC,
-                                                                      VT* __restrict__ valC, int cap_nt, const int32_t* __restrict__ items) {
-  const int cap = cap_nt & 0xFFFFFF; const bool nt = (cap_nt >> 30) & 1;      // (see spgemm_dense_vals2_kernel)
+                                                                      VT* __restrict__ valC, int cap_arg, const int32_t* __restrict__ items) {
+  const int cap = cap_arg & 0xFFFFFF;      // (see spgemm_dense_vals2_kernel)
   constexpr int H = kValTable, NT = kDenseBlock, KPT = (H / 2 + NT - 1) / NT, SG = KK_HUB_SG, NSUB = NT / SG, US = KK_HUB_US, EL = KK_HUB_EL;
   constexpr unsigned long long kSgMask = (1ull << SG) - 1ull;
   __shared__ int hk[H];
@@ -2809,7 +2555,7 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_hub_vals_kernel(const int3
     KK_UNROLL
     for (int q = 0; q < KPT; ++q) {
       const int i = t + q * NT;
-      nxtk[q]     = (i < cap && done + cap + i < cnt) ? (nt ? KK_NT_LOAD(entC + base + done + cap + i) : entC[base + done + cap + i]) : -1;
+      nxtk[q]     = (i < cap && done + cap + i < cnt) ? entC[base + done + cap + i] : -1;
     }
     __syncthreads();
     const int whi = s_whi;
@@ -2899,7 +2645,7 @@ __global__ __launch_bounds__(kDenseBlock) void spgemm_hub_vals_kernel(const int3
       if (slot[q] >= 0) {
         VT* out = valC + base + done + t + q * NT;
         if (shared_row) KK_ATOMIC_FADD(out, hv[slot[q]]);        // global_atomic_add_f64 into the row's (zeroed) values
-        else { const VT sum = first_pass ? hv[slot[q]] : *out + hv[slot[q]]; if (nt) KK_NT_STORE(out, sum); else *out = sum; }
+        else { const VT sum = first_pass ? hv[slot[q]] : *out + hv[slot[q]]; *out = sum; }
         hk[slot[q]] = -1; hv[slot[q]] = VT(0);
       }
       curk[q] = nxtk[q];
@@ -3279,12 +3025,11 @@ struct kkamd_spgemm_handle {
   bool dense_lds = false;          // decided when the numeric bins are made
   int32_t* d_hub_items = nullptr; int64_t n_hub_items = 0;      // (index, pass) pairs of the hub rows: one workgroup each
   int32_t* d_hub_multi = nullptr; int64_t n_hub_multi = 0;      // indices of the hub rows with several passes (zeroed before the launch)
-  bool hub_from_mid = false;       // the dense bin is cut [<= kValLa | <= kValLa2 | rest]: flat kernel twice, hub kernel for the rest
   int64_t n_wave_quad = 0;         // leading rows of the numeric wave bin that share waves four at a time (at most kQuadNnz entries each)
   int64_t n_dense_tiny = 0;        // leading rows of the dense bin that take the flat value kernel's lightest shape,
   int64_t n_dense_small = 0;       // rows after them that take its light shape (few entries in C and in A)
-  int64_t n_dense_lds = 0;         // leading rows of the dense bin taken by the LDS value kernel,
-  int64_t n_dense_hub_lds = 0;     // then rows for the LDS hub kernel; the rest accumulate in HBM
+  int64_t n_dense_lds = 0;         // leading rows of the dense bin with at most kValLa entries in the A row (of them the tiny and the small rows),
+  int64_t n_dense_hub_lds = 0;     // then rows with at most kValLa2 (the flat value kernel's 1024-list shape); the rest: the hub kernel, or all of the bin in HBM
   // options (kkamd_spgemm_set; the reference's SPGEMMHandle / KokkosKernelsHandle setters)
   int algorithm = 0;               // 0 hash accumulators in LDS (SPGEMM_KK and its aliases), 1 dense accumulator numeric (SPGEMM_KK_DENSE)
   int compression = 0;             // symbolic phase: 0 never compress B (default: measured 3.19 -> 3.75 ms on 27-pt 100^3 A*A although it removes
@@ -3413,7 +3158,7 @@ static int launch_dense_cols(int64_t nrows, const int32_t* perm, const OffT* rmA
   if (win_cap > 0 && win > win_cap) win = win_cap;        // lighter rows: smaller windows, more workgroups per CU, several passes
   if (win > k) win = ceil_div(k, 64) * 64;
   const size_t smem = (size_t)(win / 8);
-  const int64_t quads = (g_spgemm.col_quads && ((uintptr_t)entB % 16 == 0) && nnzB >= 4 && !maskB) ? nnzB : (int64_t)0;
+  const int64_t quads = (((uintptr_t)entB % 16 == 0) && nnzB >= 4 && !maskB) ? nnzB : (int64_t)0;
 #ifndef KK_EMU
 #define KK_DC_ATTR(QQ) KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_dense_cols_kernel<OffT, EMIT, QQ>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem))
 #else
@@ -3564,7 +3309,7 @@ struct Deferred {
 // scratch: 4 n + 4 (kSizeClasses + 1) bytes of the caller's (then nothing is allocated, nothing waited for)
 static size_t order_list_scratch_bytes(int64_t n) { return sizeof(int32_t) * (size_t)n + sizeof(unsigned) * (kSizeClasses + 1) + 16; }
 static int order_list_by_size(int32_t* list, int64_t n, const int64_t* sizes, hipStream_t st, Deferred* later = nullptr, void* scratch = nullptr) {
-  if (n < 4096 || !g_spgemm.sort_rows) return KKAMD_OK;          // (a short list finishes in one wave of workgroups whatever its order)
+  if (n < 4096) return KKAMD_OK;                                 // (a short list finishes in one wave of workgroups whatever its order)
   DevBuf tmp_b, hist_b;
   struct Hand { Deferred* d; DevBuf &a, &b; ~Hand() { if (d) { d->take(a); d->take(b); } } } hand{later, tmp_b, hist_b};
   int32_t* d_tmp; unsigned* d_hist;
@@ -3775,7 +3520,6 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
   // Without B compression (the default) nothing between the row flops and the bins depends on the host: flops, sortedness of B and the bin
   // counts are queued together and read back in one copy.
   const bool merged = !h->compression;
-  const BinLimits& symL = g_spgemm.sym_large ? kSymLimits : kSymLimitsNoLarge;
   DevBuf stats_b;                            // frees itself on every return
   unsigned long long* d_stats = h->d_small + kSmallStats;
   if (merged) KK_HIP(hipMemsetAsync(h->d_small, 0, kSmallSlots * sizeof(unsigned long long), st));
@@ -3803,7 +3547,7 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
       KK_LAUNCH((rows_sorted_long_kernel<OffT>), (unsigned)ceil_div(n, kBlock), kBlock, 0, st, n, rmB, entB, d_flag);
     }
     const int64_t* d_fl = h->d_sizes;
-    KK_LAUNCH(spgemm_bin_count_kernel, (unsigned)ceil_div(m, kBlock), kBlock, 0, st, m, d_fl, k, symL, h->d_small + kSmallBins);
+    KK_LAUNCH(spgemm_bin_count_kernel, (unsigned)ceil_div(m, kBlock), kBlock, 0, st, m, d_fl, k, kSymLimits, h->d_small + kSmallBins);
     KK_HIP(hipMemcpyAsync(h->h_small, h->d_small, kSmallSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     KK_HIP(hipStreamSynchronize(st));
     h_stats[0] = h->h_small[kSmallStats]; h_stats[1] = h->h_small[kSmallStats + 1];
@@ -3896,7 +3640,7 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
                                                (int32_t*)nullptr, k, (int64_t)0, sg, st, endB, maskB))) return rc;
     }
   } else {
-    if ((rc = make_bins(m, h->d_sizes, k, symL, h->d_perm, &off, st, merged ? h->d_small + kSmallBins : nullptr, merged ? h->h_small + kSmallBins : nullptr, merged))) return rc;   // a C row cannot exceed k columns
+    if ((rc = make_bins(m, h->d_sizes, k, kSymLimits, h->d_perm, &off, st, merged ? h->d_small + kSmallBins : nullptr, merged ? h->h_small + kSmallBins : nullptr, merged))) return rc;   // a C row cannot exceed k columns
     // When there is a dense class, the kernels of the other rows go to a second stream and run beside it (they are bound by their
     // latency chains and leave most of the chip idle: 5 of the symbolic phase's 40 ms on R-MAT scale 20 when they ran first on the one stream).
     // The caller's stream waits for them before the counts are scanned.
@@ -3925,8 +3669,6 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
     }
     if (nb(2)) KK_LAUNCH((spgemm_sym_block_kernel<OffT, kSymBlkS, kBlock>), (unsigned)nb(2), kBlock, 0, sx, nb(2),
                          (const int32_t*)(h->d_perm + off.off[2]), rmA, entA, rmB, entB, rmC, sg);
-    if (nb(3)) KK_LAUNCH((spgemm_sym_block_kernel<OffT, kSymBlkL, kDenseBlock>), (unsigned)nb(3), kDenseBlock, 0, sx, nb(3),
-                         (const int32_t*)(h->d_perm + off.off[3]), rmA, entA, rmB, entB, rmC, sg);
     if (forked) {                                              // (recorded now; the caller's stream waits for it after the dense class)
       if (hipEventRecord(h->ev_join, h->aux) != hipSuccess) { (void)hipGetLastError(); KK_HIP(hipStreamSynchronize(h->aux)); forked = false; }
     }
@@ -3986,7 +3728,7 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
             if (pool_cap > 0 && hipMalloc((void**)&h->d_pool_off, sizeof(long long) * (size_t)m) == hipSuccess &&
                 hipMemsetAsync(h->d_pool_off, 0xFF, sizeof(long long) * (size_t)m, st) == hipSuccess) {
               h->d_ent_pool = (int32_t*)((char*)h->d_bm_store + got_store); h->pool_cap = pool_cap;
-              bs.pool = h->d_ent_pool; bs.pool_off = h->d_pool_off; bs.pool_cursor = h->d_bm_counter + 1; bs.pool_cap = pool_cap; bs.list_staged = g_spgemm.list_staged;
+              bs.pool = h->d_ent_pool; bs.pool_off = h->d_pool_off; bs.pool_cursor = h->d_bm_counter + 1; bs.pool_cap = pool_cap;
             } else (void)hipGetLastError();
           } else { (void)hipGetLastError(); free_bitmap_store(h); }
         } else (void)hipGetLastError();
@@ -4043,528 +3785,545 @@ static int symbolic_typed(kkamd_spgemm_handle* h, int64_t m, int64_t n, int64_t 
   return KKAMD_OK;
 }
 
-template <class OffT, class VT>
-static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const void* rmA_, const int32_t* entA, const void* valA_,
-                         const void* rmB_, const int32_t* entB, const void* valB_, const void* rmC_, int32_t* entC,
-                         void* valC_, hipStream_t st) {
-  const OffT* rmA = (const OffT*)rmA_; const OffT* rmB = (const OffT*)rmB_; const OffT* rmC = (const OffT*)rmC_;
-  const VT* valA  = (const VT*)valA_;  const VT* valB  = (const VT*)valB_;  VT* valC = (VT*)valC_;
+// One numeric call: its arrays, typed.  numeric_typed cuts the phase into the steps below.
+template <class OffT, class VT> struct NumericCall {
+  int64_t k;
+  const OffT* rmA; const int32_t* entA; const VT* valA;
+  const OffT* rmB; const int32_t* entB; const VT* valB;
+  const OffT* rmC; int32_t* entC; VT* valC;
+  hipStream_t st;
+};
+// Rows every VALUE kernel took in one numeric call.  The dispatch writes them where it launches the kernels and numeric_report prints them; the
+// exact-value tests read that line to prove that their cases reached every kernel.
+struct NumericRows {
+  int64_t quad = 0, wave = 0;                        // wave bin: four rows per wave / one
+  int64_t block_small = 0, block_large = 0;          // block hash kernel, 4096 / 8192 slots (B unsorted)
+  int64_t blocks = 0;                                // column-block rows: as ITEMS, position- (rank) / column-indexed (direct), or with one workgroup per (row, block)
+  int64_t items_rank = 0, items_direct = 0, blocks_wg = 0;
+  int64_t win128 = 0, win256 = 0, win512 = 0, win1024 = 0;   // the flat value windows by work-items
+  int64_t hub = 0, hub_multi = 0;                    // hub rows; those of them in several passes, one workgroup per (row, pass)
+  int64_t hbm = 0;                                   // k-wide HBM accumulator
+};
+
+// Step 1, once per symbolic phase: rows of C by their exact size -> the bins of h->num_off, and the dense bin cut into the classes of its value kernels
+//   B sorted:   [ tiny | small | A row <= kValLa | A row <= kValLa2 | longer A rows (hub kernel) | column-block rows ]
+//   otherwise:  every dense row accumulates in HBM
+template <class OffT>
+static int numeric_make_bins(kkamd_spgemm_handle* h, int64_t m, int64_t k, const OffT* rmA, const OffT* rmC, hipStream_t st) {
   int rc;
-  if (!h->numeric_bins_ready) {
-    const int64_t nbk = ceil_div(m, kBlock);
-    KK_LAUNCH((spgemm_rowsize_kernel<OffT>), (unsigned)(nbk < 65536 ? nbk : 65536), kBlock, 0, st, m, rmC, h->d_sizes);
-    // SPGEMM_KK_DENSE (a21, sparse/impl/KokkosSparse_spgemm_impl_speed.hpp:28-150): every row accumulates into a k-wide dense
-    // accumulator (here: in HBM, one per concurrently processed row) instead of an LDS hash table
-    const bool dense_alg = h->algorithm == 1;
-    h->dense_lds = h->b_sorted && !g_spgemm.force_unsorted && !dense_alg;
-    if ((rc = make_bins(m, h->d_sizes, INT64_MAX, dense_alg ? kAllDense : (h->dense_lds ? kNumLimitsSorted : kNumLimits), h->d_perm, &h->num_off, st, ensure_small(h) ? h->d_small + kSmallBins : nullptr, h->h_small ? h->h_small + kSmallBins : nullptr, false))) return rc;
-    h->n_dense_lds = 0; h->n_dense_hub_lds = 0;
-    const int64_t nd = h->num_off.off[5] - h->num_off.off[4];
-    if (nd > 0) {
-      // dense bin -> [ A row <= kValLa | A row <= kHubLa | the rest ]; everything is "the rest" when B is not sorted
-      DevBuf tmp_b, cnt_b;                     // free themselves on every early return below
-      unsigned long long h_cnt[2] = {0, 0};
-      KK_HIP(tmp_b.alloc(sizeof(int32_t) * (size_t)nd));
-      KK_HIP(cnt_b.alloc(2 * sizeof(unsigned long long)));
-      int32_t* d_tmp = tmp_b.as<int32_t>(); unsigned long long* d_cnt = cnt_b.as<unsigned long long>();
-      int32_t* seg = h->d_perm + h->num_off.off[4];
-      // the tail of the bin: rows for the column-block value kernel (dense rows, and rows with more lists than the flat shapes hold)
-      h->n_dense_block = 0; h->cidx_ready = false; h->items_ready = false;
-      if (g_spgemm.block && h->dense_lds && g_spgemm.val_kernel == 2 && k >= 64) {
-        int wshift = 6;
-        while ((1 << wshift) < g_spgemm.block_w) ++wshift;
-        const int64_t nblk = ceil_div(k, (int64_t)1 << wshift);
-        size_t free_b = 0, total_b = 0;
-        const bool fits = nblk <= 65535 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)(nblk + 1) * (size_t)h->n * 4 <= free_b / 16;
-        (void)hipGetLastError();
-        if (fits) {
-          KK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), st));
-          KK_HIP(hipMemcpyAsync(d_tmp, seg, sizeof(int32_t) * (size_t)nd, hipMemcpyDeviceToDevice, st));
-          const int64_t cnt_min = (k * g_spgemm.block_min_pct + 99) / 100, cnt_floor = (k * g_spgemm.block_la_pct + 99) / 100;
-          KK_LAUNCH((spgemm_split_block_kernel<OffT>), (unsigned)ceil_div(nd, kBlock), kBlock, 0, st, nd, (const int32_t*)d_tmp, rmA, (const int64_t*)h->d_sizes,
-                    (int64_t)kValLa, cnt_min > 1 ? cnt_min : 1, cnt_floor > 1 ? cnt_floor : 1, seg, d_cnt);
-          KK_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-          KK_HIP(hipStreamSynchronize(st));
-          h->n_dense_block = (int64_t)h_cnt[1];
-          if (h->n_dense_block * kDenseBlock >= ((int64_t)1 << 32)) h->n_dense_block = 0;      // (a grid dimension holds 2^32 work-items; the split stays: every row is still in the bin once)
-          // the class's own index of C ((blocks + 1) x rows x 4 bytes) and its items (at most one 32-byte head and two 8-byte records per row and block)
-          // must fit beside the index of B: a small block width or a large k with many class rows makes them GBs.  No room: the rows keep the windowed kernels.
-          if ((double)(nblk + 1) * (double)h->n_dense_block * (4.0 + 48.0) + (double)(nblk + 1) * (double)h->n * 4.0 > (double)free_b / 8.0) h->n_dense_block = 0;
-          if ((rc = order_list_by_size(seg + (nd - h->n_dense_block), h->n_dense_block, (const int64_t*)h->d_sizes, st))) return rc;
-        }
-      }
-      int64_t lo = 0, len = nd - h->n_dense_block;
-      // (B sorted: the hub value kernel takes A rows of any length, kHubLa entries per pass; hub_chunked 0 = rows above kHubLa accumulate in HBM)
-      // flat value kernel (default): [A row <= kValLa | <= kValLa2 (the flat kernel, 1024 lists per pass) | the rest (hub kernel in passes)]
-      h->hub_from_mid = h->dense_lds && g_spgemm.val_kernel == 2 && g_spgemm.val_mid && g_spgemm.hub_chunked;
-      const int64_t la_max[2] = {g_spgemm.val_la < kValLa ? g_spgemm.val_la : kValLa,
-                                 h->hub_from_mid ? (int64_t)g_spgemm.val_la2 : (g_spgemm.hub_chunked ? INT64_MAX : (int64_t)kHubLa)};
-      int64_t first[2] = {0, 0};
-      for (int pass = 0; pass < 2 && len > 0; ++pass) {
+  const int64_t nbk = ceil_div(m, kBlock);
+  KK_LAUNCH((spgemm_rowsize_kernel<OffT>), (unsigned)(nbk < 65536 ? nbk : 65536), kBlock, 0, st, m, rmC, h->d_sizes);
+  // SPGEMM_KK_DENSE (a21, sparse/impl/KokkosSparse_spgemm_impl_speed.hpp:28-150): every row accumulates into a k-wide dense
+  // accumulator (here: in HBM, one per concurrently processed row) instead of an LDS hash table
+  const bool dense_alg = h->algorithm == 1;
+  h->dense_lds = h->b_sorted && !g_spgemm.force_unsorted && !dense_alg;
+  if ((rc = make_bins(m, h->d_sizes, INT64_MAX, dense_alg ? kAllDense : (h->dense_lds ? kNumLimitsSorted : kNumLimits), h->d_perm, &h->num_off, st, ensure_small(h) ? h->d_small + kSmallBins : nullptr, h->h_small ? h->h_small + kSmallBins : nullptr, false))) return rc;
+  h->n_dense_lds = 0; h->n_dense_hub_lds = 0;
+  const int64_t nd = h->num_off.off[5] - h->num_off.off[4];
+  if (nd > 0) {
+    // dense bin -> [ A row <= kValLa | A row <= kValLa2 | the rest ]; everything is "the rest" (the HBM accumulator's) when B is not sorted
+    DevBuf tmp_b, cnt_b;                     // free themselves on every early return below
+    unsigned long long h_cnt[2] = {0, 0};
+    KK_HIP(tmp_b.alloc(sizeof(int32_t) * (size_t)nd));
+    KK_HIP(cnt_b.alloc(2 * sizeof(unsigned long long)));
+    int32_t* d_tmp = tmp_b.as<int32_t>(); unsigned long long* d_cnt = cnt_b.as<unsigned long long>();
+    int32_t* seg = h->d_perm + h->num_off.off[4];
+    // the tail of the bin: rows for the column-block value kernel (dense rows, and rows with more lists than the flat shapes hold)
+    h->n_dense_block = 0; h->cidx_ready = false; h->items_ready = false;
+    if (g_spgemm.block && h->dense_lds && k >= 64) {
+      int wshift = 6;
+      while ((1 << wshift) < g_spgemm.block_w) ++wshift;
+      const int64_t nblk = ceil_div(k, (int64_t)1 << wshift);
+      size_t free_b = 0, total_b = 0;
+      const bool fits = nblk <= 65535 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && (size_t)(nblk + 1) * (size_t)h->n * 4 <= free_b / 16;
+      (void)hipGetLastError();
+      if (fits) {
         KK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), st));
-        KK_HIP(hipMemcpyAsync(d_tmp, seg + lo, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToDevice, st));
-        KK_LAUNCH((spgemm_split_dense_kernel<OffT>), (unsigned)ceil_div(len, kBlock), kBlock, 0, st, len, (const int32_t*)d_tmp, rmA,
-                  la_max[pass], h->dense_lds ? 0 : 1, seg + lo, d_cnt);
+        KK_HIP(hipMemcpyAsync(d_tmp, seg, sizeof(int32_t) * (size_t)nd, hipMemcpyDeviceToDevice, st));
+        const int64_t cnt_min = (k * g_spgemm.block_min_pct + 99) / 100, cnt_floor = (k * g_spgemm.block_la_pct + 99) / 100;
+        KK_LAUNCH((spgemm_split_block_kernel<OffT>), (unsigned)ceil_div(nd, kBlock), kBlock, 0, st, nd, (const int32_t*)d_tmp, rmA, (const int64_t*)h->d_sizes,
+                  (int64_t)kValLa, cnt_min > 1 ? cnt_min : 1, cnt_floor > 1 ? cnt_floor : 1, seg, d_cnt);
         KK_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
         KK_HIP(hipStreamSynchronize(st));
-        first[pass] = (int64_t)h_cnt[0];
-        lo += first[pass]; len -= first[pass];
-      }
-      h->n_dense_lds = first[0]; h->n_dense_hub_lds = first[1];
-      h->n_dense_small = 0; h->n_dense_tiny = 0;
-      if (first[0] > 0 && h->dense_lds && g_spgemm.val_kernel == 2) {
-        // [ lightest shape | light shape | the 512-work-item shape ]
-        const int64_t lim_la[2] = {kValLaTiny, kValLaSmall}, lim_cnt[2] = {g_spgemm.val_tiny_cnt, g_spgemm.val_small_cnt};
-        int64_t got[2] = {0, 0}, at = 0, left = first[0];
-        const int64_t* d_sz = h->d_sizes;
-        for (int lvl = 0; lvl < 2 && left > 0; ++lvl) {
-          if (lim_cnt[lvl] <= 0) continue;
-          KK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), st));
-          KK_HIP(hipMemcpyAsync(d_tmp, seg + at, sizeof(int32_t) * (size_t)left, hipMemcpyDeviceToDevice, st));
-          KK_LAUNCH((spgemm_split_small_kernel<OffT>), (unsigned)ceil_div(left, kBlock), kBlock, 0, st, left, (const int32_t*)d_tmp, rmA, d_sz,
-                    lim_la[lvl], lim_cnt[lvl], seg + at, d_cnt);
-          KK_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-          KK_HIP(hipStreamSynchronize(st));
-          got[lvl] = (int64_t)h_cnt[0]; at += got[lvl]; left -= got[lvl];
-        }
-        h->n_dense_tiny = got[0]; h->n_dense_small = got[1];
-      }
-      // every launch's rows largest first (the hub rows' (row, pass) items are ordered by passes further down)
-      if (h->dense_lds && g_spgemm.val_kernel == 2) {
-        const int64_t cuts[5] = {0, h->n_dense_tiny, h->n_dense_tiny + h->n_dense_small, first[0], first[0] + first[1]};
-        for (int sgi = 0; sgi < 4; ++sgi)
-          if ((rc = order_list_by_size(seg + cuts[sgi], cuts[sgi + 1] - cuts[sgi], (const int64_t*)h->d_sizes, st))) return rc;
+        h->n_dense_block = (int64_t)h_cnt[1];
+        if (h->n_dense_block * kDenseBlock >= ((int64_t)1 << 32)) h->n_dense_block = 0;      // (a grid dimension holds 2^32 work-items; the split stays: every row is still in the bin once)
+        // the class's own index of C ((blocks + 1) x rows x 4 bytes) and its items (at most one 32-byte head and two 8-byte records per row and block)
+        // must fit beside the index of B: a small block width or a large k with many class rows makes them GBs.  No room: the rows keep the windowed kernels.
+        if ((double)(nblk + 1) * (double)h->n_dense_block * (4.0 + 48.0) + (double)(nblk + 1) * (double)h->n * 4.0 > (double)free_b / 8.0) h->n_dense_block = 0;
+        if ((rc = order_list_by_size(seg + (nd - h->n_dense_block), h->n_dense_block, (const int64_t*)h->d_sizes, st))) return rc;
       }
     }
-    h->n_wave_quad = 0;
-    {
-      const int64_t nw = h->num_off.off[2] - h->num_off.off[1];
-      if (nw > 0 && !dense_alg) {
-        if (g_spgemm.quad_rows == 2 || (g_spgemm.quad_rows == 1 && h->max_row_nnz > 0 && h->max_row_nnz <= (int64_t)kQuadNnz)) h->n_wave_quad = nw;
-        else if (g_spgemm.quad_rows == 1 && (rc = split_list_by_size<OffT>(h->d_perm + h->num_off.off[1], nw, rmA, (const int64_t*)h->d_sizes, (int64_t)kQuadNnz, &h->n_wave_quad, st))) return rc;
-      }
+    int64_t lo = 0, len = nd - h->n_dense_block;
+    // B sorted: [A row <= kValLa | <= kValLa2 (the flat kernel, 1024 lists per pass) | the rest (the hub kernel, kHubLa entries per pass)]
+    const int64_t la_max[2] = {kValLa, kValLa2};
+    int64_t first[2] = {0, 0};
+    for (int pass = 0; pass < 2 && len > 0; ++pass) {
+      KK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), st));
+      KK_HIP(hipMemcpyAsync(d_tmp, seg + lo, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToDevice, st));
+      KK_LAUNCH((spgemm_split_dense_kernel<OffT>), (unsigned)ceil_div(len, kBlock), kBlock, 0, st, len, (const int32_t*)d_tmp, rmA,
+                la_max[pass], h->dense_lds ? 0 : 1, seg + lo, d_cnt);
+      KK_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+      KK_HIP(hipStreamSynchronize(st));
+      first[pass] = (int64_t)h_cnt[0];
+      lo += first[pass]; len -= first[pass];
     }
-    h->numeric_bins_ready = true;
-    if (h->d_emit_perm) { (void)hipFree(h->d_emit_perm); h->d_emit_perm = nullptr; h->n_emit_stored = 0; }
-    if (h->d_emit_perm2) { (void)hipFree(h->d_emit_perm2); h->d_emit_perm2 = nullptr; h->n_emit_pooled = 0; }
-    if (h->d_emit_perm3) { (void)hipFree(h->d_emit_perm3); h->d_emit_perm3 = nullptr; h->emit3_src = nullptr; h->emit3_n = 0; h->n_emit_sort = 0; }
-    if (h->d_hub_items) { (void)hipFree(h->d_hub_items); h->d_hub_items = nullptr; h->n_hub_items = 0; }
-    if (h->d_hub_multi) { (void)hipFree(h->d_hub_multi); h->d_hub_multi = nullptr; h->n_hub_multi = 0; }
+    h->n_dense_lds = first[0]; h->n_dense_hub_lds = first[1];
+    h->n_dense_small = 0; h->n_dense_tiny = 0;
+    if (first[0] > 0 && h->dense_lds) {
+      // [ lightest shape | light shape | the 512-work-item shape ]
+      const int64_t lim_la[2] = {kValLaTiny, kValLaSmall}, lim_cnt[2] = {g_spgemm.val_tiny_cnt, g_spgemm.val_small_cnt};
+      int64_t got[2] = {0, 0}, at = 0, left = first[0];
+      const int64_t* d_sz = h->d_sizes;
+      for (int lvl = 0; lvl < 2 && left > 0; ++lvl) {
+        if (lim_cnt[lvl] <= 0) continue;
+        KK_HIP(hipMemsetAsync(d_cnt, 0, 2 * sizeof(unsigned long long), st));
+        KK_HIP(hipMemcpyAsync(d_tmp, seg + at, sizeof(int32_t) * (size_t)left, hipMemcpyDeviceToDevice, st));
+        KK_LAUNCH((spgemm_split_small_kernel<OffT>), (unsigned)ceil_div(left, kBlock), kBlock, 0, st, left, (const int32_t*)d_tmp, rmA, d_sz,
+                  lim_la[lvl], lim_cnt[lvl], seg + at, d_cnt);
+        KK_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+        KK_HIP(hipStreamSynchronize(st));
+        got[lvl] = (int64_t)h_cnt[0]; at += got[lvl]; left -= got[lvl];
+      }
+      h->n_dense_tiny = got[0]; h->n_dense_small = got[1];
+    }
+    // every launch's rows largest first (the hub rows' (row, pass) items are ordered by passes further down)
+    if (h->dense_lds) {
+      const int64_t cuts[5] = {0, h->n_dense_tiny, h->n_dense_tiny + h->n_dense_small, first[0], first[0] + first[1]};
+      for (int sgi = 0; sgi < 4; ++sgi)
+        if ((rc = order_list_by_size(seg + cuts[sgi], cuts[sgi + 1] - cuts[sgi], (const int64_t*)h->d_sizes, st))) return rc;
+    }
   }
+  h->n_wave_quad = 0;
+  {
+    const int64_t nw = h->num_off.off[2] - h->num_off.off[1];
+    if (nw > 0 && !dense_alg) {
+      if (g_spgemm.quad_rows == 2 || (g_spgemm.quad_rows == 1 && h->max_row_nnz > 0 && h->max_row_nnz <= (int64_t)kQuadNnz)) h->n_wave_quad = nw;
+      else if (g_spgemm.quad_rows == 1 && (rc = split_list_by_size<OffT>(h->d_perm + h->num_off.off[1], nw, rmA, (const int64_t*)h->d_sizes, (int64_t)kQuadNnz, &h->n_wave_quad, st))) return rc;
+    }
+  }
+  h->numeric_bins_ready = true;
+  if (h->d_emit_perm) { (void)hipFree(h->d_emit_perm); h->d_emit_perm = nullptr; h->n_emit_stored = 0; }
+  if (h->d_emit_perm2) { (void)hipFree(h->d_emit_perm2); h->d_emit_perm2 = nullptr; h->n_emit_pooled = 0; }
+  if (h->d_emit_perm3) { (void)hipFree(h->d_emit_perm3); h->d_emit_perm3 = nullptr; h->emit3_src = nullptr; h->emit3_n = 0; h->n_emit_sort = 0; }
+  if (h->d_hub_items) { (void)hipFree(h->d_hub_items); h->d_hub_items = nullptr; h->n_hub_items = 0; }
+  if (h->d_hub_multi) { (void)hipFree(h->d_hub_multi); h->d_hub_multi = nullptr; h->n_hub_multi = 0; }
+  return KKAMD_OK;
+}
+
+// Step 2: the rows below the dense bin -- the hash kernels write their entries and values in one pass
+template <class OffT, class VT>
+static void numeric_hash_rows(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, NumericRows* rows) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const VT* valA = c.valA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const VT* valB = c.valB;
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; VT* valC = c.valC; hipStream_t st = c.st;
   const BinOffsets& off = h->num_off;
   const int sg = h->sg_log2;
   auto nb = [&](int b) { return off.off[b + 1] - off.off[b]; };
-  if (h->verbose)
-    KK_VERBOSE("\tkkamd spgemm numeric (%s): rows per kernel -- wave hash %lld, block hash small %lld, block hash large %lld, dense rows %lld "
-           "(column blocks %lld, LDS value windows %lld, LDS hub windows %lld, HBM accumulator %lld)\n", h->algorithm == 1 ? "SPGEMM_KK_DENSE" : "SPGEMM_KK",
-           (long long)nb(1), (long long)nb(2), (long long)nb(3), (long long)nb(4), (long long)h->n_dense_block, (long long)h->n_dense_lds, (long long)h->n_dense_hub_lds,
-           (long long)(nb(4) - h->n_dense_block - h->n_dense_lds - h->n_dense_hub_lds));
   if (nb(1)) {
     const int64_t nq = h->n_wave_quad < nb(1) ? h->n_wave_quad : nb(1);
     const int32_t* wlist = h->d_perm + off.off[1];
+    rows->quad = nq; rows->wave = nb(1) - nq;
     if (nq)
       KK_LAUNCH((spgemm_num_quad_kernel<OffT, VT>), (unsigned)ceil_div(nq, 4 * (kBlock / 64)), kBlock, 0, st, nq, wlist, rmA, entA, valA, rmB, entB, valB, rmC, entC, valC);
     if (nb(1) - nq)
       KK_LAUNCH((spgemm_num_wave_kernel<OffT, VT>), (unsigned)ceil_div(nb(1) - nq, kBlock / 64), kBlock, 0, st, nb(1) - nq, wlist + nq, rmA, entA, valA, rmB, entB, valB,
                 rmC, entC, valC, sg);
   }
+  rows->block_small = nb(2); rows->block_large = nb(3);
   if (nb(2)) KK_LAUNCH((spgemm_num_block_kernel<OffT, VT, kNumBlkS>), (unsigned)nb(2), kBlock, 0, st, nb(2),
                        (const int32_t*)(h->d_perm + off.off[2]), rmA, entA, valA, rmB, entB, valB, rmC, entC, valC, sg);
   if (nb(3)) KK_LAUNCH((spgemm_num_block_kernel<OffT, VT, kNumBlkL>), (unsigned)nb(3), kBlock, 0, st, nb(3),
                        (const int32_t*)(h->d_perm + off.off[3]), rmA, entA, valA, rmB, entB, valB, rmC, entC, valC, sg);
-  DevBuf acc_b;
-  VT* d_acc = nullptr;
-  // The reference's plug-in contract fills entries(C) only while !are_entries_computed()
-  // (sparse/tpls/KokkosSparse_spgemm_numeric_tpl_spec_decl.hpp:288-329): a repeated numeric call on the same handle and the same
-  // C arrays (new values of A / B, same structure) keeps the entries the previous call wrote.  What is skipped is the separate
-  // structure pass of the dense rows (the LDS bitmap kernel: 116 of 398 ms on R-MAT scale 20); the hash kernels of the short
-  // rows emit entries and values in one pass and rewrite the same entries.
-  const bool keep_entries = h->entries_valid && h->entC_ptr == (const void*)entC && h->rmC_ptr == rmC_;
-  h->entries_reused = false;
-  // entries(C) of dense-bin rows that have to walk their products: the rows with few products are sorted in LDS (spgemm_emit_sort_kernel),
-  // the others go through the bitmap kernel.  The split of `list` is made once per handle and list.
-  auto emit_walk = [&](int64_t n, const int32_t* list, int64_t win_cap) -> int {
-    int64_t nsort = 0;
-    h->sorted_used = 0;
-    if (g_spgemm.emit_sort && h->d_flop_cls && h->algorithm == 0 && n > 0) {
-      if (!h->d_emit_perm3 || h->emit3_src != list || h->emit3_n != n) {
-        if (h->d_emit_perm3) { (void)hipFree(h->d_emit_perm3); h->d_emit_perm3 = nullptr; }
-        DevBuf c4;
-        KK_HIP(c4.alloc(2 * sizeof(unsigned long long)));
-        KK_HIP(hipMemsetAsync(c4.p, 0, 2 * sizeof(unsigned long long), st));
-        KK_HIP(hipMalloc((void**)&h->d_emit_perm3, sizeof(int32_t) * (size_t)n));
-        int32_t* d_ep3 = h->d_emit_perm3; const int32_t* d_cls = h->d_flop_cls; unsigned long long* d_c4 = c4.as<unsigned long long>();
-        KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(n, kBlock), kBlock, 0, st, n, list, d_cls, d_ep3, d_c4);
-        unsigned long long h_c4[2] = {0, 0};
-        KK_HIP(hipMemcpyAsync(h_c4, c4.p, sizeof h_c4, hipMemcpyDeviceToHost, st));
-        KK_HIP(hipStreamSynchronize(st));
-        h->n_emit_sort = (int64_t)h_c4[0]; h->emit3_src = list; h->emit3_n = n;
-      }
-      nsort = h->n_emit_sort; list = h->d_emit_perm3;
-      if (nsort) KK_LAUNCH((spgemm_emit_sort_kernel<OffT>), (unsigned)nsort, kBlock, 0, st, list, rmA, entA, rmB, entB, rmC, entC);
-      h->sorted_used = nsort;
+}
+
+// entries(C) of dense-bin rows that have to walk their products: the rows with few products are sorted in LDS (spgemm_emit_sort_kernel),
+// the others go through the bitmap kernel.  The split of `list` is made once per handle and list.
+template <class OffT, class VT>
+static int numeric_emit_walk(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, int64_t n, const int32_t* list, int64_t win_cap) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const OffT* rmC = c.rmC; int32_t* entC = c.entC;
+  const int64_t k = c.k; hipStream_t st = c.st;
+  const int sg = h->sg_log2;
+  int64_t nsort = 0;
+  h->sorted_used = 0;
+  if (g_spgemm.emit_sort && h->d_flop_cls && h->algorithm == 0 && n > 0) {
+    if (!h->d_emit_perm3 || h->emit3_src != list || h->emit3_n != n) {
+      if (h->d_emit_perm3) { (void)hipFree(h->d_emit_perm3); h->d_emit_perm3 = nullptr; }
+      DevBuf c4;
+      KK_HIP(c4.alloc(2 * sizeof(unsigned long long)));
+      KK_HIP(hipMemsetAsync(c4.p, 0, 2 * sizeof(unsigned long long), st));
+      KK_HIP(hipMalloc((void**)&h->d_emit_perm3, sizeof(int32_t) * (size_t)n));
+      int32_t* d_ep3 = h->d_emit_perm3; const int32_t* d_cls = h->d_flop_cls; unsigned long long* d_c4 = c4.as<unsigned long long>();
+      KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(n, kBlock), kBlock, 0, st, n, list, d_cls, d_ep3, d_c4);
+      unsigned long long h_c4[2] = {0, 0};
+      KK_HIP(hipMemcpyAsync(h_c4, c4.p, sizeof h_c4, hipMemcpyDeviceToHost, st));
+      KK_HIP(hipStreamSynchronize(st));
+      h->n_emit_sort = (int64_t)h_c4[0]; h->emit3_src = list; h->emit3_n = n;
     }
-    if (n - nsort) return launch_dense_cols<OffT, true>(n - nsort, list + nsort, rmA, entA, rmB, entB, (OffT*)nullptr, rmC, entC, k, h->nnzB, sg, st, nullptr, nullptr,
-                                                        BitmapStore(), win_cap);
-    return KKAMD_OK;
-  };
-  auto emit_units = [&](hipStream_t sq, int) {
-    const UnitHead* d_hd = h->d_heads; const int32_t* d_ur = h->d_row_slot; const unsigned* d_uc = h->d_ucnt; const unsigned* d_co = h->d_ucoff;
-    const char* d_st = (const char*)h->d_bm_store;
-    const int64_t min_nnz = (h->dense_lds ? kNumLimitsSorted : kNumLimits).lim[3];
-#define KK_EMIT_UNIT(NTT) KK_LAUNCH((spgemm_emit_unit_kernel<OffT, NTT>), (unsigned)h->n_heads, NTT, 0, sq, d_hd, d_ur, h->unit_nwin, h->unit_wb, k, d_uc, d_co, d_st, rmC, entC, min_nnz)
-    KK_EMIT_UNIT(256);
-#undef KK_EMIT_UNIT
-  };
-  if (nb(4)) {
-    const int32_t* dperm = h->d_perm + off.off[4];
-    // entries(C) of every dense row, column-sorted
-    if (keep_entries) h->entries_reused = true;
-    else if (h->unit_mode && h->unit_rows_kept > 0 && h->algorithm == 0) {
-      // the symbolic phase's units: rows whose every unit kept its structure are written unit by unit (bitmaps, entry lists); the others walk their products
-      if (!h->d_emit_perm) {
-        DevBuf c2;
-        KK_HIP(c2.alloc(3 * sizeof(unsigned long long)));
-        KK_HIP(hipMemsetAsync(c2.p, 0, 3 * sizeof(unsigned long long), st));
-        KK_HIP(hipMalloc((void**)&h->d_emit_perm, sizeof(int32_t) * (size_t)nb(4)));
-        int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; unsigned long long* d_c2 = c2.as<unsigned long long>();
-        KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(nb(4), kBlock), kBlock, 0, st, nb(4), dperm, d_rs, d_ep, d_c2);
-        KK_LAUNCH(spgemm_count_flag_kernel, (unsigned)ceil_div(nb(4), kBlock), kBlock, 0, st, nb(4), dperm, d_rs, d_c2 + 2);
-        unsigned long long h_c2[3] = {0, 0, 0};
-        KK_HIP(hipMemcpyAsync(h_c2, c2.p, sizeof h_c2, hipMemcpyDeviceToHost, st));
-        KK_HIP(hipStreamSynchronize(st));
-        h->n_emit_stored = (int64_t)h_c2[0]; h->n_emit_pooled = (int64_t)h_c2[2];
-      }
-      const int64_t ns = h->n_emit_stored, nr = nb(4) - ns;
-      if (ns && h->n_heads) {
-        // (Measured and not kept: the units of the column-block rows first and the others' on the second stream beside the column-block value kernels --
-        // the two 13 ms halves overlapped, and the value kernel beside the second took 26.3 instead of 13.5 ms: both live on the memory system.)
-        emit_units(st, -1);
-      }
-      if (nr && (rc = emit_walk(nr, h->d_emit_perm + ns, (int64_t)g_spgemm.emit_win_bits))) return rc;
-      h->bitmaps_used = ns; h->pooled_used = h->n_emit_pooled;
+    nsort = h->n_emit_sort; list = h->d_emit_perm3;
+    if (nsort) KK_LAUNCH((spgemm_emit_sort_kernel<OffT>), (unsigned)nsort, kBlock, 0, st, list, rmA, entA, rmB, entB, rmC, entC);
+    h->sorted_used = nsort;
+  }
+  if (n - nsort) return launch_dense_cols<OffT, true>(n - nsort, list + nsort, rmA, entA, rmB, entB, (OffT*)nullptr, rmC, entC, k, h->nnzB, sg, st, nullptr, nullptr,
+                                                      BitmapStore(), win_cap);
+  return KKAMD_OK;
+}
+
+// Step 3: entries(C) of every dense row, column-sorted -- from what the symbolic phase kept (units, bitmaps, entry lists) where it kept something
+template <class OffT, class VT>
+static int numeric_emit_entries(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c) {
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; const int64_t k = c.k; hipStream_t st = c.st;
+  const int64_t n4 = h->num_off.off[5] - h->num_off.off[4];
+  const int32_t* dperm = h->d_perm + h->num_off.off[4];
+  int rc;
+  if (h->unit_mode && h->unit_rows_kept > 0 && h->algorithm == 0) {
+    // the symbolic phase's units: rows whose every unit kept its structure are written unit by unit (bitmaps, entry lists); the others walk their products
+    if (!h->d_emit_perm) {
+      DevBuf c2;
+      KK_HIP(c2.alloc(3 * sizeof(unsigned long long)));
+      KK_HIP(hipMemsetAsync(c2.p, 0, 3 * sizeof(unsigned long long), st));
+      KK_HIP(hipMalloc((void**)&h->d_emit_perm, sizeof(int32_t) * (size_t)n4));
+      int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; unsigned long long* d_c2 = c2.as<unsigned long long>();
+      KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(n4, kBlock), kBlock, 0, st, n4, dperm, d_rs, d_ep, d_c2);
+      KK_LAUNCH(spgemm_count_flag_kernel, (unsigned)ceil_div(n4, kBlock), kBlock, 0, st, n4, dperm, d_rs, d_c2 + 2);
+      unsigned long long h_c2[3] = {0, 0, 0};
+      KK_HIP(hipMemcpyAsync(h_c2, c2.p, sizeof h_c2, hipMemcpyDeviceToHost, st));
+      KK_HIP(hipStreamSynchronize(st));
+      h->n_emit_stored = (int64_t)h_c2[0]; h->n_emit_pooled = (int64_t)h_c2[2];
     }
-    else if (h->d_bm_store && (h->bm_stored > 0 || h->pool_used > 0) && h->algorithm == 0) {
-      // rows whose bitmap the symbolic phase kept are written from it; the others walk their products
-      if (!h->d_emit_perm) {
-        DevBuf c2;
-        KK_HIP(c2.alloc(2 * sizeof(unsigned long long)));
-        KK_HIP(hipMemsetAsync(c2.p, 0, 2 * sizeof(unsigned long long), st));
-        KK_HIP(hipMalloc((void**)&h->d_emit_perm, sizeof(int32_t) * (size_t)nb(4)));
-        int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; unsigned long long* d_c2 = c2.as<unsigned long long>();
-        KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(nb(4), kBlock), kBlock, 0, st, nb(4), dperm, d_rs, d_ep, d_c2);
-        unsigned long long h_c2[2] = {0, 0};
-        KK_HIP(hipMemcpyAsync(h_c2, c2.p, sizeof h_c2, hipMemcpyDeviceToHost, st));
-        KK_HIP(hipStreamSynchronize(st));
-        h->n_emit_stored = (int64_t)h_c2[0];
-      }
-      const int64_t ns = h->n_emit_stored, nr = nb(4) - ns;
-      if (ns) {
-        const int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; const kk_u64* d_st = (const kk_u64*)h->d_bm_store;
-        KK_LAUNCH((spgemm_emit_bitmap_kernel<OffT>), (unsigned)ns, kDenseBlock, 0, st, d_ep, d_rs, d_st, h->bm_words, rmC, entC, g_spgemm.emit_staged);
-      }
-      int64_t np = 0;                                            // of the others: rows whose entry list the symbolic phase left in the pool
-      const int32_t* rest = h->d_emit_perm + ns;
-      if (nr && h->d_pool_off && h->pool_used > 0) {
-        if (!h->d_emit_perm2) {
-          DevBuf c3;
-          KK_HIP(c3.alloc(2 * sizeof(unsigned long long)));
-          KK_HIP(hipMemsetAsync(c3.p, 0, 2 * sizeof(unsigned long long), st));
-          KK_HIP(hipMalloc((void**)&h->d_emit_perm2, sizeof(int32_t) * (size_t)nr));
-          int32_t* d_ep2 = h->d_emit_perm2; const long long* d_po = h->d_pool_off; unsigned long long* d_c3 = c3.as<unsigned long long>();
-          KK_LAUNCH((spgemm_split_stored_kernel<long long>), (unsigned)ceil_div(nr, kBlock), kBlock, 0, st, nr, rest, d_po, d_ep2, d_c3);
-          unsigned long long h_c3[2] = {0, 0};
-          KK_HIP(hipMemcpyAsync(h_c3, c3.p, sizeof h_c3, hipMemcpyDeviceToHost, st));
-          KK_HIP(hipStreamSynchronize(st));
-          h->n_emit_pooled = (int64_t)h_c3[0];
-        }
-        np = h->n_emit_pooled; rest = h->d_emit_perm2;
-        if (np) {
-          const long long* d_po = h->d_pool_off; const int32_t* d_pl = h->d_ent_pool;
-          KK_LAUNCH((spgemm_copy_pool_kernel<OffT>), (unsigned)np, kBlock, 0, st, rest, d_po, d_pl, rmC, entC);
-        }
-      }
-      if (nr - np && (rc = emit_walk(nr - np, rest + np, (int64_t)g_spgemm.emit_win_bits))) return rc;
-      h->bitmaps_used = ns; h->pooled_used = np;
+    const int64_t ns = h->n_emit_stored, nr = n4 - ns;
+    if (ns && h->n_heads) {
+      // (Measured and not kept: the units of the column-block rows first and the others' on the second stream beside the column-block value kernels --
+      // the two 13 ms halves overlapped, and the value kernel beside the second took 26.3 instead of 13.5 ms: both live on the memory system.)
+      const UnitHead* d_hd = h->d_heads; const unsigned* d_uc = h->d_ucnt; const unsigned* d_co = h->d_ucoff;
+      const int64_t min_nnz = (h->dense_lds ? kNumLimitsSorted : kNumLimits).lim[3];
+      KK_LAUNCH((spgemm_emit_unit_kernel<OffT, 256>), (unsigned)h->n_heads, 256, 0, st, d_hd, h->d_row_slot, h->unit_nwin, h->unit_wb, k, d_uc, d_co, (const char*)h->d_bm_store, rmC, entC, min_nnz);
     }
-    else if ((rc = emit_walk(nb(4), dperm, (int64_t)0))) return rc;
-#define KK_VALS2(HH, NTT, GG, LAA, GRID, PERM, CAP)                                                                                     \
-  do {                                                                                                                                  \
-    KK_LAUNCH((spgemm_dense_vals2_kernel<OffT, VT, HH, NTT, GG, LAA, 0>), (unsigned)(GRID), NTT, 0, st, PERM, rmA, entA, valA, rmB, entB, valB, \
-              rmC, (const int32_t*)entC, valC, (CAP) | (g_spgemm.nt ? (1 << 30) : 0), h->nnzB KK_DBG_ARG);                             \
-  } while (0)
-    const int64_t n_blk = h->n_dense_block;
-    const int64_t n_lds = h->n_dense_lds; int64_t n_hubl = h->n_dense_hub_lds, n_hub = nb(4) - n_blk - n_lds - n_hubl;
-    const bool flat_vals = g_spgemm.val_kernel == 2 && h->dense_lds;
-    if (n_blk) {
-      // column-block value kernel: the index of B (kept while B's arrays and the block grid are the same), the index of these rows'
-      // entries(C) (once per symbolic phase: it depends on the structure only), then one workgroup per (row, block), block-major
-      int wshift = 6;
-      while ((1 << wshift) < g_spgemm.block_w) ++wshift;
-      const int nblk = (int)ceil_div(k, (int64_t)1 << wshift);
-      const int64_t nB = h->n;
-      const int32_t* bperm = dperm + (nb(4) - n_blk);
-      if (!h->d_bidx || h->bidx_rmB != rmB_ || h->bidx_entB != (const void*)entB || h->bidx_nB != nB || h->bidx_nblk != nblk || h->bidx_wshift != wshift) {
-        if (h->d_bidx) { (void)hipFree(h->d_bidx); h->d_bidx = nullptr; }
-        KK_HIP(hipMalloc((void**)&h->d_bidx, sizeof(unsigned) * (size_t)(nblk + 1) * (size_t)nB));
-        unsigned* d_bx = h->d_bidx;
-        KK_LAUNCH((spgemm_bidx_kernel<OffT>), (unsigned)ceil_div((int64_t)(nblk + 1) * nB, kBlock), kBlock, 0, st, nB, nblk, wshift, rmB, entB, d_bx);
-        h->bidx_rmB = rmB_; h->bidx_entB = entB; h->bidx_nB = nB; h->bidx_nblk = nblk; h->bidx_wshift = wshift;
-      }
-      if (h->idx_nblk != nblk || h->idx_wshift != wshift) { h->cidx_ready = false; h->items_ready = false; }
-      if (h->items_cap != g_spgemm.item_cap || h->items_blocks != g_spgemm.item_blocks) h->items_ready = false;
-      if (!h->cidx_ready) {
-        h->idx_nblk = nblk; h->idx_wshift = wshift;
-        if (h->d_cidx) { (void)hipFree(h->d_cidx); h->d_cidx = nullptr; }
-        KK_HIP(hipMalloc((void**)&h->d_cidx, sizeof(unsigned) * (size_t)(nblk + 1) * (size_t)n_blk));
-        unsigned* d_cx = h->d_cidx;
-        KK_LAUNCH((spgemm_cidx_kernel<OffT>), (unsigned)ceil_div((int64_t)(nblk + 1) * n_blk, kBlock), kBlock, 0, st, n_blk, bperm, nblk, wshift, rmC, (const int32_t*)entC, d_cx);
-        h->cidx_ready = true;
-      }
-      const size_t smem = sizeof(VT) << wshift;
-      const unsigned* d_bx = h->d_bidx; const unsigned* d_cx = h->d_cidx;
-      const bool use_items = g_spgemm.items && nblk <= 4096 && wshift >= 5;
-      if (use_items && !h->items_ready) {
-        // the class's items, once per symbolic phase (they depend on the structure of C only): count, scan, fill, order by first block
-        if (h->d_items_rank) { (void)hipFree(h->d_items_rank); h->d_items_rank = nullptr; }
-        if (h->d_items_direct) { (void)hipFree(h->d_items_direct); h->d_items_direct = nullptr; }
-        h->n_items_rank = 0; h->n_items_direct = 0;
-        DevBuf nr_b, nd_b, hist_b, tmp_r, tmp_d;
-        KK_HIP(nr_b.alloc(sizeof(unsigned) * (size_t)(n_blk + 1))); KK_HIP(nd_b.alloc(sizeof(unsigned) * (size_t)(n_blk + 1)));
-        unsigned* d_nr = nr_b.as<unsigned>(); unsigned* d_nd = nd_b.as<unsigned>();
-        KK_HIP(hipMemsetAsync(d_nr, 0, sizeof(unsigned) * (size_t)(n_blk + 1), st)); KK_HIP(hipMemsetAsync(d_nd, 0, sizeof(unsigned) * (size_t)(n_blk + 1), st));
-        const unsigned cap_items = (unsigned)g_spgemm.item_cap;
-        const unsigned bgrid = (unsigned)ceil_div(n_blk, kBlock);
-        KK_LAUNCH(spgemm_items_build_kernel, bgrid, kBlock, 0, st, n_blk, nblk, d_cx, cap_items, g_spgemm.item_blocks, 0, d_nr, d_nd, (int2*)nullptr, (int2*)nullptr);
-        if ((rc = exclusive_scan_inplace<unsigned>(d_nr, n_blk + 1, st))) return rc;
-        if ((rc = exclusive_scan_inplace<unsigned>(d_nd, n_blk + 1, st))) return rc;
-        unsigned h_tot[2] = {0, 0};
-        KK_HIP(hipMemcpyAsync(&h_tot[0], d_nr + n_blk, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        KK_HIP(hipMemcpyAsync(&h_tot[1], d_nd + n_blk, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    if (nr && (rc = numeric_emit_walk(h, c, nr, h->d_emit_perm + ns, (int64_t)g_spgemm.emit_win_bits))) return rc;
+    h->bitmaps_used = ns; h->pooled_used = h->n_emit_pooled;
+  }
+  else if (h->d_bm_store && (h->bm_stored > 0 || h->pool_used > 0) && h->algorithm == 0) {
+    // rows whose bitmap the symbolic phase kept are written from it; the others walk their products
+    if (!h->d_emit_perm) {
+      DevBuf c2;
+      KK_HIP(c2.alloc(2 * sizeof(unsigned long long)));
+      KK_HIP(hipMemsetAsync(c2.p, 0, 2 * sizeof(unsigned long long), st));
+      KK_HIP(hipMalloc((void**)&h->d_emit_perm, sizeof(int32_t) * (size_t)n4));
+      int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; unsigned long long* d_c2 = c2.as<unsigned long long>();
+      KK_LAUNCH((spgemm_split_stored_kernel<int32_t>), (unsigned)ceil_div(n4, kBlock), kBlock, 0, st, n4, dperm, d_rs, d_ep, d_c2);
+      unsigned long long h_c2[2] = {0, 0};
+      KK_HIP(hipMemcpyAsync(h_c2, c2.p, sizeof h_c2, hipMemcpyDeviceToHost, st));
+      KK_HIP(hipStreamSynchronize(st));
+      h->n_emit_stored = (int64_t)h_c2[0];
+    }
+    const int64_t ns = h->n_emit_stored, nr = n4 - ns;
+    if (ns) {
+      const int32_t* d_ep = h->d_emit_perm; const int32_t* d_rs = h->d_row_slot; const kk_u64* d_st = (const kk_u64*)h->d_bm_store;
+      KK_LAUNCH((spgemm_emit_bitmap_kernel<OffT>), (unsigned)ns, kDenseBlock, 0, st, d_ep, d_rs, d_st, h->bm_words, rmC, entC);
+    }
+    int64_t np = 0;                                            // of the others: rows whose entry list the symbolic phase left in the pool
+    const int32_t* rest = h->d_emit_perm + ns;
+    if (nr && h->d_pool_off && h->pool_used > 0) {
+      if (!h->d_emit_perm2) {
+        DevBuf c3;
+        KK_HIP(c3.alloc(2 * sizeof(unsigned long long)));
+        KK_HIP(hipMemsetAsync(c3.p, 0, 2 * sizeof(unsigned long long), st));
+        KK_HIP(hipMalloc((void**)&h->d_emit_perm2, sizeof(int32_t) * (size_t)nr));
+        int32_t* d_ep2 = h->d_emit_perm2; const long long* d_po = h->d_pool_off; unsigned long long* d_c3 = c3.as<unsigned long long>();
+        KK_LAUNCH((spgemm_split_stored_kernel<long long>), (unsigned)ceil_div(nr, kBlock), kBlock, 0, st, nr, rest, d_po, d_ep2, d_c3);
+        unsigned long long h_c3[2] = {0, 0};
+        KK_HIP(hipMemcpyAsync(h_c3, c3.p, sizeof h_c3, hipMemcpyDeviceToHost, st));
         KK_HIP(hipStreamSynchronize(st));
-        KK_HIP(tmp_r.alloc(sizeof(int2) * (size_t)(h_tot[0] ? h_tot[0] : 1))); KK_HIP(tmp_d.alloc(sizeof(int2) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
-        DevBuf ord_r, ord_d;                       // the items ordered by first block; what the value kernels read are the heads made of them
-        KK_HIP(ord_r.alloc(sizeof(int2) * (size_t)(h_tot[0] ? h_tot[0] : 1))); KK_HIP(ord_d.alloc(sizeof(int2) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
-        KK_HIP(hipMalloc((void**)&h->d_items_rank, sizeof(ItemHead) * (size_t)(h_tot[0] ? h_tot[0] : 1)));
-        KK_HIP(hipMalloc((void**)&h->d_items_direct, sizeof(ItemHead) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
-        int2* t_r = tmp_r.as<int2>(); int2* t_d = tmp_d.as<int2>();
-        KK_LAUNCH(spgemm_items_build_kernel, bgrid, kBlock, 0, st, n_blk, nblk, d_cx, cap_items, g_spgemm.item_blocks, 1, d_nr, d_nd, t_r, t_d);
-        KK_HIP(hist_b.alloc(sizeof(unsigned) * (size_t)(nblk + 1)));
-        unsigned* d_hist = hist_b.as<unsigned>();
-        for (int which = 0; which < 2; ++which) {
-          const int64_t n_it = h_tot[which];
-          if (!n_it) continue;
-          const int2* src = which == 0 ? t_r : t_d; int2* dst = which == 0 ? ord_r.as<int2>() : ord_d.as<int2>();
-          KK_HIP(hipMemsetAsync(d_hist, 0, sizeof(unsigned) * (size_t)(nblk + 1), st));
-          const int64_t nbk_it = ceil_div(n_it, kBlock);
-          const unsigned g_it = (unsigned)(nbk_it < 2048 ? nbk_it : 2048);
-          KK_LAUNCH(spgemm_items_hist_kernel, g_it, kBlock, 0, st, n_it, src, nblk, d_hist);
-          KK_LAUNCH(spgemm_items_scan_kernel, 1, 64, 0, st, nblk, d_hist);
-          KK_LAUNCH(spgemm_items_scatter_kernel, g_it, kBlock, 0, st, n_it, src, nblk, d_hist, dst);
-          KK_LAUNCH((spgemm_items_head_kernel<OffT>), (unsigned)nbk_it, kBlock, 0, st, n_it, (const int2*)dst, bperm, nblk, d_cx, rmA, rmC,
-                    which == 0 ? h->d_items_rank : h->d_items_direct);
-        }
-        KK_HIP(hipStreamSynchronize(st));              // the scratch buffers go out of scope
-        h->n_items_rank = h_tot[0]; h->n_items_direct = h_tot[1]; h->items_ready = true; h->items_cap = g_spgemm.item_cap; h->items_blocks = g_spgemm.item_blocks;
-        if (h->verbose) KK_VERBOSE("\tkkamd spgemm numeric: column-block class: %lld rows as %lld position-indexed items (<= %u entries, <= %d blocks) and %lld column-indexed blocks\n",
-                                   (long long)n_blk, (long long)h->n_items_rank, cap_items, g_spgemm.item_blocks, (long long)h->n_items_direct);
+        h->n_emit_pooled = (int64_t)h_c3[0];
       }
-      if (use_items) {
-        const ItemHead* d_ir = h->d_items_rank; const ItemHead* d_id = h->d_items_direct;
-        if (h->n_items_direct) {
+      np = h->n_emit_pooled; rest = h->d_emit_perm2;
+      if (np) {
+        const long long* d_po = h->d_pool_off; const int32_t* d_pl = h->d_ent_pool;
+        KK_LAUNCH((spgemm_copy_pool_kernel<OffT>), (unsigned)np, kBlock, 0, st, rest, d_po, d_pl, rmC, entC);
+      }
+    }
+    if (nr - np && (rc = numeric_emit_walk(h, c, nr - np, rest + np, (int64_t)g_spgemm.emit_win_bits))) return rc;
+    h->bitmaps_used = ns; h->pooled_used = np;
+  }
+  else if ((rc = numeric_emit_walk(h, c, n4, dperm, (int64_t)0))) return rc;
+  return KKAMD_OK;
+}
+
+// Step 4a: the column-block rows.  The index of B (kept while B's arrays and the block grid are the same), the index of these rows' entries(C)
+// (once per symbolic phase: it depends on the structure only), then the rows as ITEMS or one workgroup per (row, block), block-major
+template <class OffT, class VT>
+static int numeric_block_values(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, const int32_t* bperm, int64_t n_blk, NumericRows* rows) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const VT* valA = c.valA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const VT* valB = c.valB;
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; VT* valC = c.valC; const int64_t k = c.k; hipStream_t st = c.st;
+  int rc;
+  rows->blocks = n_blk;
+  int wshift = 6;
+  while ((1 << wshift) < g_spgemm.block_w) ++wshift;
+  const int nblk = (int)ceil_div(k, (int64_t)1 << wshift);
+  const int64_t nB = h->n;
+  if (!h->d_bidx || h->bidx_rmB != (const void*)rmB || h->bidx_entB != (const void*)entB || h->bidx_nB != nB || h->bidx_nblk != nblk || h->bidx_wshift != wshift) {
+    if (h->d_bidx) { (void)hipFree(h->d_bidx); h->d_bidx = nullptr; }
+    KK_HIP(hipMalloc((void**)&h->d_bidx, sizeof(unsigned) * (size_t)(nblk + 1) * (size_t)nB));
+    unsigned* d_bx = h->d_bidx;
+    KK_LAUNCH((spgemm_bidx_kernel<OffT>), (unsigned)ceil_div((int64_t)(nblk + 1) * nB, kBlock), kBlock, 0, st, nB, nblk, wshift, rmB, entB, d_bx);
+    h->bidx_rmB = rmB; h->bidx_entB = entB; h->bidx_nB = nB; h->bidx_nblk = nblk; h->bidx_wshift = wshift;
+  }
+  if (h->idx_nblk != nblk || h->idx_wshift != wshift) { h->cidx_ready = false; h->items_ready = false; }
+  if (h->items_cap != g_spgemm.item_cap || h->items_blocks != g_spgemm.item_blocks) h->items_ready = false;
+  if (!h->cidx_ready) {
+    h->idx_nblk = nblk; h->idx_wshift = wshift;
+    if (h->d_cidx) { (void)hipFree(h->d_cidx); h->d_cidx = nullptr; }
+    KK_HIP(hipMalloc((void**)&h->d_cidx, sizeof(unsigned) * (size_t)(nblk + 1) * (size_t)n_blk));
+    unsigned* d_cx = h->d_cidx;
+    KK_LAUNCH((spgemm_cidx_kernel<OffT>), (unsigned)ceil_div((int64_t)(nblk + 1) * n_blk, kBlock), kBlock, 0, st, n_blk, bperm, nblk, wshift, rmC, (const int32_t*)entC, d_cx);
+    h->cidx_ready = true;
+  }
+  const size_t smem = sizeof(VT) << wshift;
+  const unsigned* d_bx = h->d_bidx; const unsigned* d_cx = h->d_cidx;
+  const bool use_items = g_spgemm.items && nblk <= 4096 && wshift >= 5;
+  if (use_items && !h->items_ready) {
+    // the class's items, once per symbolic phase (they depend on the structure of C only): count, scan, fill, order by first block
+    if (h->d_items_rank) { (void)hipFree(h->d_items_rank); h->d_items_rank = nullptr; }
+    if (h->d_items_direct) { (void)hipFree(h->d_items_direct); h->d_items_direct = nullptr; }
+    h->n_items_rank = 0; h->n_items_direct = 0;
+    DevBuf nr_b, nd_b, hist_b, tmp_r, tmp_d;
+    KK_HIP(nr_b.alloc(sizeof(unsigned) * (size_t)(n_blk + 1))); KK_HIP(nd_b.alloc(sizeof(unsigned) * (size_t)(n_blk + 1)));
+    unsigned* d_nr = nr_b.as<unsigned>(); unsigned* d_nd = nd_b.as<unsigned>();
+    KK_HIP(hipMemsetAsync(d_nr, 0, sizeof(unsigned) * (size_t)(n_blk + 1), st)); KK_HIP(hipMemsetAsync(d_nd, 0, sizeof(unsigned) * (size_t)(n_blk + 1), st));
+    const unsigned cap_items = (unsigned)g_spgemm.item_cap;
+    const unsigned bgrid = (unsigned)ceil_div(n_blk, kBlock);
+    KK_LAUNCH(spgemm_items_build_kernel, bgrid, kBlock, 0, st, n_blk, nblk, d_cx, cap_items, g_spgemm.item_blocks, 0, d_nr, d_nd, (int2*)nullptr, (int2*)nullptr);
+    if ((rc = exclusive_scan_inplace<unsigned>(d_nr, n_blk + 1, st))) return rc;
+    if ((rc = exclusive_scan_inplace<unsigned>(d_nd, n_blk + 1, st))) return rc;
+    unsigned h_tot[2] = {0, 0};
+    KK_HIP(hipMemcpyAsync(&h_tot[0], d_nr + n_blk, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    KK_HIP(hipMemcpyAsync(&h_tot[1], d_nd + n_blk, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    KK_HIP(hipStreamSynchronize(st));
+    KK_HIP(tmp_r.alloc(sizeof(int2) * (size_t)(h_tot[0] ? h_tot[0] : 1))); KK_HIP(tmp_d.alloc(sizeof(int2) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
+    DevBuf ord_r, ord_d;                       // the items ordered by first block; what the value kernels read are the heads made of them
+    KK_HIP(ord_r.alloc(sizeof(int2) * (size_t)(h_tot[0] ? h_tot[0] : 1))); KK_HIP(ord_d.alloc(sizeof(int2) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
+    KK_HIP(hipMalloc((void**)&h->d_items_rank, sizeof(ItemHead) * (size_t)(h_tot[0] ? h_tot[0] : 1)));
+    KK_HIP(hipMalloc((void**)&h->d_items_direct, sizeof(ItemHead) * (size_t)(h_tot[1] ? h_tot[1] : 1)));
+    int2* t_r = tmp_r.as<int2>(); int2* t_d = tmp_d.as<int2>();
+    KK_LAUNCH(spgemm_items_build_kernel, bgrid, kBlock, 0, st, n_blk, nblk, d_cx, cap_items, g_spgemm.item_blocks, 1, d_nr, d_nd, t_r, t_d);
+    KK_HIP(hist_b.alloc(sizeof(unsigned) * (size_t)(nblk + 1)));
+    unsigned* d_hist = hist_b.as<unsigned>();
+    for (int which = 0; which < 2; ++which) {
+      const int64_t n_it = h_tot[which];
+      if (!n_it) continue;
+      const int2* src = which == 0 ? t_r : t_d; int2* dst = which == 0 ? ord_r.as<int2>() : ord_d.as<int2>();
+      KK_HIP(hipMemsetAsync(d_hist, 0, sizeof(unsigned) * (size_t)(nblk + 1), st));
+      const int64_t nbk_it = ceil_div(n_it, kBlock);
+      const unsigned g_it = (unsigned)(nbk_it < 2048 ? nbk_it : 2048);
+      KK_LAUNCH(spgemm_items_hist_kernel, g_it, kBlock, 0, st, n_it, src, nblk, d_hist);
+      KK_LAUNCH(spgemm_items_scan_kernel, 1, 64, 0, st, nblk, d_hist);
+      KK_LAUNCH(spgemm_items_scatter_kernel, g_it, kBlock, 0, st, n_it, src, nblk, d_hist, dst);
+      KK_LAUNCH((spgemm_items_head_kernel<OffT>), (unsigned)nbk_it, kBlock, 0, st, n_it, (const int2*)dst, bperm, nblk, d_cx, rmA, rmC,
+                which == 0 ? h->d_items_rank : h->d_items_direct);
+    }
+    KK_HIP(hipStreamSynchronize(st));              // the scratch buffers go out of scope
+    h->n_items_rank = h_tot[0]; h->n_items_direct = h_tot[1]; h->items_ready = true; h->items_cap = g_spgemm.item_cap; h->items_blocks = g_spgemm.item_blocks;
+    if (h->verbose) KK_VERBOSE("\tkkamd spgemm numeric: column-block class: %lld rows as %lld position-indexed items (<= %u entries, <= %d blocks) and %lld column-indexed blocks\n",
+                               (long long)n_blk, (long long)h->n_items_rank, cap_items, g_spgemm.item_blocks, (long long)h->n_items_direct);
+  }
+  if (use_items) {
+    rows->items_rank = h->n_items_rank; rows->items_direct = h->n_items_direct;
+    const ItemHead* d_ir = h->d_items_rank; const ItemHead* d_id = h->d_items_direct;
+    if (h->n_items_direct) {
 #ifndef KK_EMU
-          KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_item_vals_kernel<OffT, VT, kDenseBlock, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+      KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_item_vals_kernel<OffT, VT, kDenseBlock, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
 #endif
-          KK_LAUNCH((spgemm_item_vals_kernel<OffT, VT, kDenseBlock, false>), (unsigned)h->n_items_direct, kDenseBlock, smem, st, d_id, wshift, nB, d_bx,
-                    entA, valA, rmB, entB, valB, h->nnzB, (const int32_t*)entC, valC, 1);
-        }
-        if (h->n_items_rank) {
-          const size_t smem_r = (((size_t)g_spgemm.item_blocks << (wshift - 5)) * 8) + sizeof(VT) * (size_t)g_spgemm.item_cap;
+      KK_LAUNCH((spgemm_item_vals_kernel<OffT, VT, kDenseBlock, false>), (unsigned)h->n_items_direct, kDenseBlock, smem, st, d_id, wshift, nB, d_bx,
+                entA, valA, rmB, entB, valB, h->nnzB, (const int32_t*)entC, valC, 1);
+    }
+    if (h->n_items_rank) {
+      const size_t smem_r = (((size_t)g_spgemm.item_blocks << (wshift - 5)) * 8) + sizeof(VT) * (size_t)g_spgemm.item_cap;
 #ifndef KK_EMU
-          KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_item_vals_kernel<OffT, VT, kValBlock, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r));
+      KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_item_vals_kernel<OffT, VT, kValBlock, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r));
 #endif
-          KK_LAUNCH((spgemm_item_vals_kernel<OffT, VT, kValBlock, true>), (unsigned)h->n_items_rank, kValBlock, smem_r, st, d_ir, wshift, nB, d_bx,
-                    entA, valA, rmB, entB, valB, h->nnzB, (const int32_t*)entC, valC, g_spgemm.item_blocks);
-        }
-      } else {
-      // blocks of 16384 columns: one workgroup of 1024 per CU around 128 KB of sums; narrower blocks: 512 work-items, two (or more) workgroups per CU
+      KK_LAUNCH((spgemm_item_vals_kernel<OffT, VT, kValBlock, true>), (unsigned)h->n_items_rank, kValBlock, smem_r, st, d_ir, wshift, nB, d_bx,
+                entA, valA, rmB, entB, valB, h->nnzB, (const int32_t*)entC, valC, g_spgemm.item_blocks);
+    }
+  } else {
+    // blocks of 16384 columns: one workgroup of 1024 per CU around 128 KB of sums; narrower blocks: 512 work-items, two (or more) workgroups per CU
 #ifndef KK_EMU
 #define KK_BLK_ATTR(NTT) KK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&spgemm_block_vals_kernel<OffT, VT, NTT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem))
 #else
 #define KK_BLK_ATTR(NTT) (void)0
 #endif
 #define KK_BLK(NTT)                                                                                                                          \
-      do {                                                                                                                                   \
-        KK_BLK_ATTR(NTT);                                                                                                                    \
-        KK_LAUNCH((spgemm_block_vals_kernel<OffT, VT, NTT>), dim3((unsigned)n_blk, (unsigned)nblk), NTT, smem, st, n_blk, bperm, nblk, wshift, nB, d_bx, d_cx, \
-                  rmA, entA, valA, rmB, entB, valB, h->nnzB, rmC, (const int32_t*)entC, valC);                                               \
-      } while (0)
-      if (wshift >= 14) KK_BLK(kDenseBlock); else KK_BLK(kValBlock);
+    do {                                                                                                                                 \
+      KK_BLK_ATTR(NTT);                                                                                                                  \
+      KK_LAUNCH((spgemm_block_vals_kernel<OffT, VT, NTT>), dim3((unsigned)n_blk, (unsigned)nblk), NTT, smem, st, n_blk, bperm, nblk, wshift, nB, d_bx, d_cx, \
+                rmA, entA, valA, rmB, entB, valB, h->nnzB, rmC, (const int32_t*)entC, valC);                                             \
+    } while (0)
+    rows->blocks_wg = n_blk;
+    if (wshift >= 14) KK_BLK(kDenseBlock); else KK_BLK(kValBlock);
 #undef KK_BLK
 #undef KK_BLK_ATTR
-      }
-    }
-    if (flat_vals && g_spgemm.val_hub_flat) {
-      // measured and not kept as the default: A rows above kValLa through the flat kernel, kValLa lists per pass (R-MAT scale 20:
-      // numeric 353 -> 479 ms -- with thousands of lists a group of windows costs 8 x 512 searches per pass and a pass finds a
-      // handful of products per list and window; the cached-next-column sweep of spgemm_hub_vals_kernel skips the empty lists for free)
-      int cap = g_spgemm.val_cap;
-      cap = cap < 64 ? 64 : (cap > kValTable / 2 ? kValTable / 2 : cap);
-      if (n_hubl + n_hub) KK_VALS2(kValTable, kValBlock, 8, kValLa, n_hubl + n_hub, dperm + n_lds, cap);
-      n_hubl = 0; n_hub = 0;
-    }
-    if (n_hub && flat_vals && h->hub_from_mid) {      // A rows above kValLa2 entries (the heaviest rows first): the cached-cursor hub kernel, kHubLa entries per pass
-      int cap = g_spgemm.val_cap;
-      cap = cap < 64 ? 64 : (cap > kValTable / 2 ? kValTable / 2 : cap);
-      const int32_t* hperm = dperm + n_lds + n_hubl;
-      // the passes of a row that has several add into values(C) with global_atomic_add_f64: only into ordinary device memory (hardware
-      // floating-point atomics are not dependable on fine-grained / managed allocations); anything else keeps one workgroup per row, which
-      // runs the passes one after the other without atomics
-      bool plain_valc = true;
+  }
+  return KKAMD_OK;
+}
+
+// Step 4b: A rows above kValLa2 entries (the heaviest rows first): the cached-cursor hub kernel, kHubLa entries per pass
+template <class OffT, class VT>
+static int numeric_hub_values(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, const int32_t* hperm, int64_t n_hub, int cap, NumericRows* rows) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const VT* valA = c.valA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const VT* valB = c.valB;
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; VT* valC = c.valC; hipStream_t st = c.st;
+  // the passes of a row that has several add into values(C) with global_atomic_add_f64: only into ordinary device memory (hardware
+  // floating-point atomics are not dependable on fine-grained / managed allocations); anything else keeps one workgroup per row, which
+  // runs the passes one after the other without atomics
+  bool plain_valc = true;
 #ifndef KK_EMU
-      {
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, (const void*)valC) != hipSuccess) { (void)hipGetLastError(); plain_valc = false; }
-        else plain_valc = attr.type == hipMemoryTypeDevice && !attr.isManaged;
-      }
+  {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, (const void*)valC) != hipSuccess) { (void)hipGetLastError(); plain_valc = false; }
+    else plain_valc = attr.type == hipMemoryTypeDevice && !attr.isManaged;
+  }
 #endif
-      const bool hub_split = g_spgemm.hub_split && plain_valc;
-      if (hub_split && !h->d_hub_items) {            // (row, pass) items, once per set of bins
-        DevBuf pb;
-        KK_HIP(pb.alloc(sizeof(int32_t) * (size_t)n_hub));
-        int32_t* d_p = pb.as<int32_t>();
-        KK_LAUNCH((spgemm_hub_passes_kernel<OffT>), (unsigned)ceil_div(n_hub, kBlock), kBlock, 0, st, n_hub, hperm, rmA, d_p);
-        std::vector<int32_t> h_p((size_t)n_hub), h_items, h_multi;
-        KK_HIP(hipMemcpyAsync(h_p.data(), d_p, sizeof(int32_t) * (size_t)n_hub, hipMemcpyDeviceToHost, st));
-        KK_HIP(hipStreamSynchronize(st));
-        // the rows with the most passes first: their passes are the longest-running items
-        std::vector<int32_t> ord((size_t)n_hub);
-        for (int64_t i = 0; i < n_hub; ++i) ord[(size_t)i] = (int32_t)i;
-        std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return h_p[(size_t)x] > h_p[(size_t)y]; });
-        for (int32_t i : ord) {
-          for (int32_t ps = 0; ps < h_p[(size_t)i]; ++ps) { h_items.push_back(i); h_items.push_back(ps); }
-          if (h_p[(size_t)i] > 1) h_multi.push_back(i);
-        }
-        h->n_hub_items = (int64_t)h_items.size() / 2; h->n_hub_multi = (int64_t)h_multi.size();
-        KK_HIP(hipMalloc((void**)&h->d_hub_items, sizeof(int32_t) * (h_items.size() ? h_items.size() : 1)));
-        KK_HIP(hipMalloc((void**)&h->d_hub_multi, sizeof(int32_t) * (h_multi.size() ? h_multi.size() : 1)));
-        if (!h_items.empty()) KK_HIP(hipMemcpyAsync(h->d_hub_items, h_items.data(), sizeof(int32_t) * h_items.size(), hipMemcpyHostToDevice, st));
-        if (!h_multi.empty()) KK_HIP(hipMemcpyAsync(h->d_hub_multi, h_multi.data(), sizeof(int32_t) * h_multi.size(), hipMemcpyHostToDevice, st));
-        KK_HIP(hipStreamSynchronize(st));
-      }
-      if (hub_split && h->d_hub_items && h->n_hub_items > 0) {
-        const int32_t* d_items = h->d_hub_items; const int32_t* d_multi = h->d_hub_multi;
-        if (h->n_hub_multi) KK_LAUNCH((spgemm_zero_rows_kernel<OffT, VT>), (unsigned)h->n_hub_multi, kBlock, 0, st, hperm, d_multi, rmC, valC);
-        KK_LAUNCH((spgemm_hub_vals_kernel<OffT, VT>), (unsigned)h->n_hub_items, kDenseBlock, 0, st, hperm, rmA, entA, valA, rmB, entB, valB,
-                  rmC, (const int32_t*)entC, valC, cap | (g_spgemm.nt ? (1 << 30) : 0), d_items);
-      } else {
-        KK_LAUNCH((spgemm_hub_vals_kernel<OffT, VT>), (unsigned)n_hub, kDenseBlock, 0, st, hperm, rmA, entA, valA, rmB, entB, valB,
-                  rmC, (const int32_t*)entC, valC, cap | (g_spgemm.nt ? (1 << 30) : 0), (const int32_t*)nullptr);
-      }
-      n_hub = 0;
+  if (plain_valc && !h->d_hub_items) {            // (row, pass) items, once per set of bins
+    DevBuf pb;
+    KK_HIP(pb.alloc(sizeof(int32_t) * (size_t)n_hub));
+    int32_t* d_p = pb.as<int32_t>();
+    KK_LAUNCH((spgemm_hub_passes_kernel<OffT>), (unsigned)ceil_div(n_hub, kBlock), kBlock, 0, st, n_hub, hperm, rmA, d_p);
+    std::vector<int32_t> h_p((size_t)n_hub), h_items, h_multi;
+    KK_HIP(hipMemcpyAsync(h_p.data(), d_p, sizeof(int32_t) * (size_t)n_hub, hipMemcpyDeviceToHost, st));
+    KK_HIP(hipStreamSynchronize(st));
+    // the rows with the most passes first: their passes are the longest-running items
+    std::vector<int32_t> ord((size_t)n_hub);
+    for (int64_t i = 0; i < n_hub; ++i) ord[(size_t)i] = (int32_t)i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return h_p[(size_t)x] > h_p[(size_t)y]; });
+    for (int32_t i : ord) {
+      for (int32_t ps = 0; ps < h_p[(size_t)i]; ++ps) { h_items.push_back(i); h_items.push_back(ps); }
+      if (h_p[(size_t)i] > 1) h_multi.push_back(i);
     }
-    if (n_hubl && flat_vals && h->hub_from_mid) {    // A rows of kValLa + 1 .. kValLa2 entries: the flat kernel with 1024 lists per pass
-      int cap = g_spgemm.val_cap;
-      cap = cap < 64 ? 64 : (cap > kValTable / 2 ? kValTable / 2 : cap);
-      KK_VALS2(kValTable, kDenseBlock, 4, kValLa2, n_hubl, dperm + n_lds, cap);
-      n_hubl = 0;
-    }
-    if (n_hubl) {      // heaviest rows first
-      int cap = g_spgemm.val_cap;
-      cap = cap < 64 ? 64 : (cap > kValTable / 2 ? kValTable / 2 : cap);
-      KK_LAUNCH((spgemm_hub_vals_kernel<OffT, VT>), (unsigned)n_hubl, kDenseBlock, 0, st, dperm + n_lds, rmA, entA, valA, rmB, entB, valB,
-                rmC, (const int32_t*)entC, valC, cap | (g_spgemm.nt ? (1 << 30) : 0), (const int32_t*)nullptr);
-    }
-    if (n_lds) {
-      int cap = g_spgemm.val_cap;
-      if (cap < 64) cap = 64;
-#define KK_VALS(HH, NTT)                                                                                              \
-  do {                                                                                                                \
-    if (cap > HH / 2) cap = HH / 2;                                                                                   \
-    KK_LAUNCH((spgemm_dense_vals_kernel<OffT, VT, HH, NTT>), (unsigned)n_lds, NTT, 0, st, dperm, rmA, entA, valA, rmB, \
-              entB, valB, rmC, (const int32_t*)entC, valC, cap KK_DBG_ARG);                                      \
-  } while (0)
-      if (flat_vals) {
-        if (cap > kValTable / 2) cap = kValTable / 2;
-        const int64_t n_tiny = h->n_dense_tiny < n_lds ? h->n_dense_tiny : n_lds;
-        const int64_t n_small = h->n_dense_small < n_lds - n_tiny ? h->n_dense_small : n_lds - n_tiny;
-        if (n_tiny) {                                            // the lightest shape (see spgemm_split_small_kernel)
-          const int cap_t = cap > kValTableTiny / 2 ? kValTableTiny / 2 : cap;
-          KK_VALS2(kValTableTiny, 128, 8, kValLaTiny, n_tiny, dperm, cap_t);
-        }
-        if (n_small) {                                           // the light shape for the rows with few entries
-          const int cap_s = cap > kValTableSmall / 2 ? kValTableSmall / 2 : cap;
-          KK_VALS2(kValTableSmall, kBlock, 8, kValLaSmall, n_small, dperm + n_tiny, cap_s);
-        }
-        if (n_lds - n_tiny - n_small)
-          KK_VALS2(kValTable, kValBlock, 8, kValLa, n_lds - n_tiny - n_small, dperm + n_tiny + n_small, cap);
-      } else switch (g_spgemm.val_shape) {
-        case 1: KK_VALS(8192, 1024); break;
-        case 2: KK_VALS(8192, 512); break;
-        case 3: KK_VALS(2048, 256); break;
-        case 4: KK_VALS(4096, 1024); break;
-        default: KK_VALS(kValTable, kValBlock); break;
-      }
-#undef KK_VALS
+    h->n_hub_items = (int64_t)h_items.size() / 2; h->n_hub_multi = (int64_t)h_multi.size();
+    KK_HIP(hipMalloc((void**)&h->d_hub_items, sizeof(int32_t) * (h_items.size() ? h_items.size() : 1)));
+    KK_HIP(hipMalloc((void**)&h->d_hub_multi, sizeof(int32_t) * (h_multi.size() ? h_multi.size() : 1)));
+    if (!h_items.empty()) KK_HIP(hipMemcpyAsync(h->d_hub_items, h_items.data(), sizeof(int32_t) * h_items.size(), hipMemcpyHostToDevice, st));
+    if (!h_multi.empty()) KK_HIP(hipMemcpyAsync(h->d_hub_multi, h_multi.data(), sizeof(int32_t) * h_multi.size(), hipMemcpyHostToDevice, st));
+    KK_HIP(hipStreamSynchronize(st));
+  }
+  rows->hub = n_hub;
+  if (plain_valc && h->d_hub_items && h->n_hub_items > 0) {
+    rows->hub_multi = h->n_hub_multi;
+    const int32_t* d_items = h->d_hub_items; const int32_t* d_multi = h->d_hub_multi;
+    if (h->n_hub_multi) KK_LAUNCH((spgemm_zero_rows_kernel<OffT, VT>), (unsigned)h->n_hub_multi, kBlock, 0, st, hperm, d_multi, rmC, valC);
+    KK_LAUNCH((spgemm_hub_vals_kernel<OffT, VT>), (unsigned)h->n_hub_items, kDenseBlock, 0, st, hperm, rmA, entA, valA, rmB, entB, valB,
+              rmC, (const int32_t*)entC, valC, cap, d_items);
+  } else {
+    KK_LAUNCH((spgemm_hub_vals_kernel<OffT, VT>), (unsigned)n_hub, kDenseBlock, 0, st, hperm, rmA, entA, valA, rmB, entB, valB,
+              rmC, (const int32_t*)entC, valC, cap, (const int32_t*)nullptr);
+  }
+  return KKAMD_OK;
+}
+
+// Step 4c (B unsorted, or SPGEMM_KK_DENSE): the rows accumulate in HBM.  *acc must outlive the kernels
+template <class OffT, class VT>
+static int numeric_hbm_values(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, const int32_t* perm, int64_t n_hub, DevBuf* acc, NumericRows* rows) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const VT* valA = c.valA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const VT* valB = c.valB;
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; VT* valC = c.valC; const int64_t k = c.k; hipStream_t st = c.st;
+  const int sg = h->sg_log2;
+  rows->hbm = n_hub;
+  // batches of G rows, each with its own k-wide accumulator (bounded to 1/8 of free HBM), ~256K work-items in flight
+  size_t free_b = 0, total_b = 0;
+  KK_HIP(hipMemGetInfo(&free_b, &total_b));
+  int64_t G = (int64_t)(free_b / 8) / (k * (int64_t)sizeof(VT));
+  if (G < 1) return fail(KKAMD_ERR_ALLOC, "spgemm: not enough device memory for one hub-row accumulator (%lld bytes)", (long long)(k * (int64_t)sizeof(VT)));
+  if (G > 1024) G = 1024;
+  if (G > n_hub) G = n_hub;
+  int64_t bx = 1024 / G;
+  bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
+  KK_HIP(acc->alloc((size_t)k * sizeof(VT) * (size_t)G));
+  VT* d_acc = acc->as<VT>();
+  KK_HIP(hipMemsetAsync(d_acc, 0, (size_t)k * sizeof(VT) * (size_t)G, st));
+  for (int64_t r0 = 0; r0 < n_hub; r0 += G) {
+    const unsigned g = (unsigned)(n_hub - r0 < G ? n_hub - r0 : G);
+    const int32_t* batch = perm + r0;
+    KK_LAUNCH((spgemm_hub_acc_kernel<OffT, VT>), dim3((unsigned)bx, g), kBlock, 0, st, batch, rmA, entA, valA, rmB, entB, valB, d_acc, k, sg);
+    KK_LAUNCH((spgemm_hub_extract_kernel<OffT, VT>), dim3((unsigned)bx, g), kBlock, 0, st, batch, rmC, (const int32_t*)entC, valC, d_acc, k);
+  }
+  return KKAMD_OK;
+}
+
+// Step 4: values of the dense bin.  The rule, with B sorted (numeric_make_bins cut the bin this way):
+//   column-block rows                                   -> items / blocks        (knobs block, items)
+//   A row <= kValLa entries, by the row's entries in C  -> flat windows, 128 / 256 / 512 work-items  (knobs val_tiny_cnt, val_small_cnt)
+//   A row <= kValLa2                                    -> flat windows, 1024 work-items
+//   longer A rows                                       -> hub kernel
+// and without: every row -> HBM accumulator.
+template <class OffT, class VT>
+static int numeric_launch_values(kkamd_spgemm_handle* h, const NumericCall<OffT, VT>& c, DevBuf* acc, NumericRows* rows) {
+  const OffT* rmA = c.rmA; const int32_t* entA = c.entA; const VT* valA = c.valA; const OffT* rmB = c.rmB; const int32_t* entB = c.entB; const VT* valB = c.valB;
+  const OffT* rmC = c.rmC; int32_t* entC = c.entC; VT* valC = c.valC; hipStream_t st = c.st;
+  const int64_t n4 = h->num_off.off[5] - h->num_off.off[4];
+  const int32_t* dperm = h->d_perm + h->num_off.off[4];
+  const int64_t n_blk = h->n_dense_block, n_lds = h->n_dense_lds, n_mid = h->n_dense_hub_lds, n_rest = n4 - n_blk - n_lds - n_mid;
+  int rc;
+  if (n_blk && (rc = numeric_block_values(h, c, dperm + (n4 - n_blk), n_blk, rows))) return rc;
+  if (!h->dense_lds) return n_rest ? numeric_hbm_values(h, c, dperm + n_lds + n_mid, n_rest, acc, rows) : KKAMD_OK;
+  const int cap = g_spgemm.val_cap < 64 ? 64 : (g_spgemm.val_cap > kValTable / 2 ? kValTable / 2 : g_spgemm.val_cap);      // C entries per window
+  if (n_rest && (rc = numeric_hub_values(h, c, dperm + n_lds + n_mid, n_rest, cap, rows))) return rc;
+#define KK_VALS2(HH, NTT, GG, LAA, GRID, PERM, CAP)                                                                                     \
+  KK_LAUNCH((spgemm_dense_vals2_kernel<OffT, VT, HH, NTT, GG, LAA, 0>), (unsigned)(GRID), NTT, 0, st, PERM, rmA, entA, valA, rmB, entB, valB, \
+            rmC, (const int32_t*)entC, valC, (CAP), h->nnzB KK_DBG_ARG)
+  rows->win1024 = n_mid;
+  if (n_mid) KK_VALS2(kValTable, kDenseBlock, 4, kValLa2, n_mid, dperm + n_lds, cap);
+  const int64_t n_tiny = h->n_dense_tiny < n_lds ? h->n_dense_tiny : n_lds;
+  const int64_t n_small = h->n_dense_small < n_lds - n_tiny ? h->n_dense_small : n_lds - n_tiny;
+  rows->win128 = n_tiny; rows->win256 = n_small; rows->win512 = n_lds - n_tiny - n_small;
+  if (n_tiny) {                                                // the lightest shape (see spgemm_split_small_kernel)
+    const int cap_t = cap > kValTableTiny / 2 ? kValTableTiny / 2 : cap;
+    KK_VALS2(kValTableTiny, 128, 8, kValLaTiny, n_tiny, dperm, cap_t);
+  }
+  if (n_small) {                                               // the light shape for the rows with few entries
+    const int cap_s = cap > kValTableSmall / 2 ? kValTableSmall / 2 : cap;
+    KK_VALS2(kValTableSmall, kBlock, 8, kValLaSmall, n_small, dperm + n_tiny, cap_s);
+  }
+  if (rows->win512) KK_VALS2(kValTable, kValBlock, 8, kValLa, rows->win512, dperm + n_tiny + n_small, cap);
 #undef KK_VALS2
-    }
-    if (n_hub) {
-      // batches of G rows, each with its own k-wide accumulator (bounded to 1/8 of free HBM), ~256K work-items in flight
-      size_t free_b = 0, total_b = 0;
-      KK_HIP(hipMemGetInfo(&free_b, &total_b));
-      int64_t G = (int64_t)(free_b / 8) / (k * (int64_t)sizeof(VT));
-      if (G < 1) return fail(KKAMD_ERR_ALLOC, "spgemm: not enough device memory for one hub-row accumulator (%lld bytes)", (long long)(k * (int64_t)sizeof(VT)));
-      if (G > 1024) G = 1024;
-      if (G > n_hub) G = n_hub;
-      int64_t bx = 1024 / G;
-      bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
-      KK_HIP(acc_b.alloc((size_t)k * sizeof(VT) * (size_t)G));
-      d_acc = acc_b.as<VT>();
-      KK_HIP(hipMemsetAsync(d_acc, 0, (size_t)k * sizeof(VT) * (size_t)G, st));
-      for (int64_t r0 = 0; r0 < n_hub; r0 += G) {
-        const unsigned g = (unsigned)(n_hub - r0 < G ? n_hub - r0 : G);
-        const int32_t* rows = dperm + n_lds + n_hubl + r0;
-        KK_LAUNCH((spgemm_hub_acc_kernel<OffT, VT>), dim3((unsigned)bx, g), kBlock, 0, st, rows, rmA, entA, valA, rmB, entB, valB, d_acc, k, sg);
-        KK_LAUNCH((spgemm_hub_extract_kernel<OffT, VT>), dim3((unsigned)bx, g), kBlock, 0, st, rows, rmC, (const int32_t*)entC, valC, d_acc, k);
-      }
-    }
+  return KKAMD_OK;
+}
+
+static void numeric_report(const kkamd_spgemm_handle* h, const NumericRows& r) {
+  KK_VERBOSE("\tkkamd spgemm numeric (%s): rows per value kernel -- quad=%lld wave=%lld block_small=%lld block_large=%lld blocks=%lld items_rank=%lld "
+             "items_direct=%lld blocks_wg=%lld win128=%lld win256=%lld win512=%lld win1024=%lld hub=%lld hub_multi=%lld hbm=%lld\n",
+             h->algorithm == 1 ? "SPGEMM_KK_DENSE" : "SPGEMM_KK", (long long)r.quad, (long long)r.wave, (long long)r.block_small, (long long)r.block_large,
+             (long long)r.blocks, (long long)r.items_rank, (long long)r.items_direct, (long long)r.blocks_wg, (long long)r.win128, (long long)r.win256,
+             (long long)r.win512, (long long)r.win1024, (long long)r.hub, (long long)r.hub_multi, (long long)r.hbm);
+}
+
+template <class OffT, class VT>
+static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const void* rmA_, const int32_t* entA, const void* valA_,
+                         const void* rmB_, const int32_t* entB, const void* valB_, const void* rmC_, int32_t* entC,
+                         void* valC_, hipStream_t st) {
+  const NumericCall<OffT, VT> c = {k, (const OffT*)rmA_, entA, (const VT*)valA_, (const OffT*)rmB_, entB, (const VT*)valB_, (const OffT*)rmC_, entC, (VT*)valC_, st};
+  int rc;
+  if (!h->numeric_bins_ready && (rc = numeric_make_bins<OffT>(h, m, k, c.rmA, c.rmC, st))) return rc;
+  auto nb = [&](int b) { return h->num_off.off[b + 1] - h->num_off.off[b]; };
+  if (h->verbose)
+    KK_VERBOSE("\tkkamd spgemm numeric (%s): rows per kernel -- wave hash %lld, block hash small %lld, block hash large %lld, dense rows %lld "
+           "(column blocks %lld, LDS value windows %lld, LDS hub windows %lld, HBM accumulator %lld)\n", h->algorithm == 1 ? "SPGEMM_KK_DENSE" : "SPGEMM_KK",
+           (long long)nb(1), (long long)nb(2), (long long)nb(3), (long long)nb(4), (long long)h->n_dense_block, (long long)h->n_dense_lds, (long long)h->n_dense_hub_lds,
+           (long long)(nb(4) - h->n_dense_block - h->n_dense_lds - h->n_dense_hub_lds));
+  NumericRows rows;
+  DevBuf acc;                                 // the HBM accumulators, if any: alive until the stream has drained
+  numeric_hash_rows(h, c, &rows);
+  // The reference's plug-in contract fills entries(C) only while !are_entries_computed()
+  // (sparse/tpls/KokkosSparse_spgemm_numeric_tpl_spec_decl.hpp:288-329): a repeated numeric call on the same handle and the same
+  // C arrays (new values of A / B, same structure) keeps the entries the previous call wrote.  What is skipped is the separate
+  // structure pass of the dense rows (the LDS bitmap kernel: 116 of 398 ms on R-MAT scale 20); the hash kernels of the short
+  // rows emit entries and values in one pass and rewrite the same entries.
+  h->entries_reused = nb(4) > 0 && h->entries_valid && h->entC_ptr == (const void*)entC && h->rmC_ptr == rmC_;
+  if (nb(4)) {
+    if (!h->entries_reused && (rc = numeric_emit_entries(h, c))) return rc;
+    if ((rc = numeric_launch_values(h, c, &acc, &rows))) return rc;
   }
   hipError_t e = hipGetLastError();
   hipError_t e2 = hipStreamSynchronize(st);   // the reference's numeric phase fences too (impl_kkmem.hpp:1440,1467)
   if (e != hipSuccess || e2 != hipSuccess) { h->entries_valid = false; return fail(KKAMD_ERR_HIP, "spgemm numeric failed: %s", hipGetErrorString(e != hipSuccess ? e : e2)); }
   h->entries_valid = true; h->entC_ptr = entC; h->rmC_ptr = rmC_;
-  if (h->verbose) {
-    // which VALUE kernel took how many rows (the line above counts the bins; a bin's kernel depends on B being sorted and on the knobs).
-    // The exact-value tests read this line to prove that their cases reached every kernel.
-    const bool flat = g_spgemm.val_kernel == 2 && h->dense_lds, mid = flat && h->hub_from_mid && !g_spgemm.val_hub_flat;
-    const int64_t n4 = nb(4), n_blk = n4 ? h->n_dense_block : 0, n_lds = n4 ? h->n_dense_lds : 0, n_hubl = n4 ? h->n_dense_hub_lds : 0;
-    const int64_t n_rest = n4 - n_blk - n_lds - n_hubl;
-    const int64_t n_quad = nb(1) ? (h->n_wave_quad < nb(1) ? h->n_wave_quad : nb(1)) : 0;
-    const int64_t n_tiny = flat ? (h->n_dense_tiny < n_lds ? h->n_dense_tiny : n_lds) : 0;
-    const int64_t n_small = flat ? (h->n_dense_small < n_lds - n_tiny ? h->n_dense_small : n_lds - n_tiny) : 0;
-    const bool items = n_blk && g_spgemm.items && h->items_ready && h->items_cap == g_spgemm.item_cap && h->idx_nblk <= 4096 && h->idx_wshift >= 5;
-    const int64_t n_hub_rows = g_spgemm.val_hub_flat && flat ? 0 : (mid ? n_rest : n_hubl);
-    // quad / wave: wave bin, four rows per wave / one; items_rank, items_direct: ITEMS of the column-block rows, position- / column-indexed; blocks_wg: those rows
-    // with one workgroup per (row, block); win128 .. win1024: the flat value windows by work-items; hub_multi: hub rows in several passes; hbm: k-wide accumulator
-    KK_VERBOSE("\tkkamd spgemm numeric (%s): rows per value kernel -- quad=%lld wave=%lld block_small=%lld block_large=%lld blocks=%lld items_rank=%lld "
-               "items_direct=%lld blocks_wg=%lld win128=%lld win256=%lld win512=%lld win1024=%lld hub=%lld hub_multi=%lld hbm=%lld\n",
-               h->algorithm == 1 ? "SPGEMM_KK_DENSE" : "SPGEMM_KK", (long long)n_quad, (long long)(nb(1) - n_quad), (long long)nb(2), (long long)nb(3),
-               (long long)n_blk, (long long)(items ? h->n_items_rank : 0), (long long)(items ? h->n_items_direct : 0), (long long)(n_blk && !items ? n_blk : 0),
-               (long long)n_tiny, (long long)n_small, (long long)(flat ? n_lds - n_tiny - n_small : n_lds), (long long)(mid ? n_hubl : 0),
-               (long long)n_hub_rows, (long long)(mid && h->d_hub_items ? h->n_hub_multi : 0), (long long)(flat ? (mid || g_spgemm.val_hub_flat ? 0 : n_rest) : n_rest));
-  }
+  if (h->verbose) numeric_report(h, rows);
   if (h->d_bm_store || h->unit_mode) { const int64_t used = h->bitmaps_used; free_bitmap_store(h); h->bitmaps_used = used; }    // entries(C) are written: the bitmaps (GBs) are not needed again
   return KKAMD_OK;
-}
-
-template <class OffT> __global__ void max_diff_kernel(int64_t m, const OffT* __restrict__ rm, unsigned long long* out) {
-  unsigned long long mx = 0;
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned long long l = (unsigned long long)((int64_t)rm[r + 1] - (int64_t)rm[r]);
-    mx = l > mx ? l : mx;
-  }
-  for (int o = 32; o > 0; o >>= 1) { const unsigned long long other = __shfl_xor(mx, o, 64); mx = other > mx ? other : mx; }
-  if ((threadIdx.x & 63) == 0 && mx) atomicMax(out, mx);
 }
 
 int spgemm_set_default(const char* key, int value) {
@@ -4580,22 +4339,14 @@ int spgemm_set_default(const char* key, int value) {
 #ifdef KK_ABLATE
   else if (k == "spgemm_debug") g_spgemm.debug = value;
 #endif
-  else if (k == "spgemm_val_shape") g_spgemm.val_shape = value;
-  else if (k == "spgemm_val_hub_flat") g_spgemm.val_hub_flat = value != 0;
-  else if (k == "spgemm_col_quads") { if (value != 0 && value != 1 && value != 4) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_col_quads: %d is not 0 or 4", value); g_spgemm.col_quads = value == 1 ? 4 : value; }
-  else if (k == "spgemm_hub_chunked") g_spgemm.hub_chunked = value != 0;
-  else if (k == "spgemm_val_mid") g_spgemm.val_mid = value != 0;
   else if (k == "spgemm_keep_bitmaps") g_spgemm.keep_bitmaps = value != 0;
   else if (k == "spgemm_keep_lists") g_spgemm.keep_lists = value != 0;
   else if (k == "spgemm_val_tiny_cnt") { if (value < 0) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_val_tiny_cnt: %d is negative", value); g_spgemm.val_tiny_cnt = value; }
   else if (k == "spgemm_emit_sort") g_spgemm.emit_sort = value != 0;
   else if (k == "spgemm_pool_keep") { if (value < 0 || value > 2) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_pool_keep: 0 (first product returns the store, repeat users keep it), 1 (keep) or 2 (return)"); g_spgemm.pool_keep = value; }
-  else if (k == "spgemm_sort_rows") g_spgemm.sort_rows = value != 0;
   else if (k == "spgemm_store_cap_mb") { if (value < 0) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_store_cap_mb: %d is negative", value); g_spgemm.store_cap_mb = value; }
   else if (k == "spgemm_sym_units") g_spgemm.sym_units = value != 0;
   else if (k == "spgemm_unit_bits") { if (value < 6 || value > kUnitBitsMax) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_unit_bits: 6 .. %d", kUnitBitsMax); g_spgemm.unit_bits = value; }
-  else if (k == "spgemm_nt") g_spgemm.nt = value != 0;
-  else if (k == "spgemm_list_staged") g_spgemm.list_staged = value != 0;
   else if (k == "spgemm_block") g_spgemm.block = value != 0;
   else if (k == "spgemm_items") g_spgemm.items = value != 0;
   else if (k == "spgemm_item_blocks") { if (value < 1 || value > 16) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_item_blocks: 1 .. 16"); g_spgemm.item_blocks = value; }
@@ -4605,13 +4356,7 @@ int spgemm_set_default(const char* key, int value) {
   else if (k == "spgemm_block_la_pct") { if (value < 0 || value > 100) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_block_la_pct: 0 .. 100"); g_spgemm.block_la_pct = value; }
   else if (k == "spgemm_quad_rows") { if (value < 0 || value > 2) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_quad_rows: %d is not 0, 1 or 2", value); g_spgemm.quad_rows = value; }
   else if (k == "spgemm_val_small_cnt") { if (value < 0) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_val_small_cnt: %d is negative", value); g_spgemm.val_small_cnt = value; }
-  else if (k == "spgemm_emit_staged") g_spgemm.emit_staged = value != 0;
-  else if (k == "spgemm_sym_large") g_spgemm.sym_large = value != 0;
-  else if (k == "spgemm_hub_split") g_spgemm.hub_split = value != 0;
   else if (k == "spgemm_emit_win_bits") { if (value < 0 || (value & 63)) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_emit_win_bits must be a multiple of 64"); g_spgemm.emit_win_bits = value; }
-  else if (k == "spgemm_val_la2") { if (value < kValLa2) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_val_la2 must be at least %d", kValLa2); g_spgemm.val_la2 = value; }
-  else if (k == "spgemm_val_kernel") { if (value != 1 && value != 2) return fail(KKAMD_ERR_INVALID_ARG, "spgemm_val_kernel is 1 or 2"); g_spgemm.val_kernel = value; }
-  else if (k == "spgemm_val_la") g_spgemm.val_la = value;
   else return fail(KKAMD_ERR_INVALID_ARG, "kkamd_set_default: unknown key '%s'", k.c_str());
   return KKAMD_OK;
 }

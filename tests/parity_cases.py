@@ -1080,6 +1080,22 @@ VALUE_KERNELS = ("quad", "wave", "block_small", "block_large", "items_rank", "it
                  "hub", "hub_multi", "hbm")
 KNOB_DEFAULTS = {"spgemm_block_w": 16384, "spgemm_items": 1, "spgemm_item_cap": 6144, "spgemm_quad_rows": 1, "spgemm_force_unsorted": 0,
                  "spgemm_val_cap": 2048, "spgemm_unit_bits": 18, "spgemm_win_bits": 1 << 20, "spgemm_emit_sort": 1, "spgemm_block": 1}
+# switches whose other setting selected code the library never ran by default: they went, with that code
+REMOVED_SPGEMM_KNOBS = ("spgemm_val_kernel", "spgemm_val_shape", "spgemm_val_hub_flat", "spgemm_val_mid", "spgemm_hub_chunked", "spgemm_val_la",
+                        "spgemm_val_la2", "spgemm_hub_split", "spgemm_nt", "spgemm_sort_rows", "spgemm_list_staged", "spgemm_emit_staged",
+                        "spgemm_sym_large", "spgemm_col_quads")
+
+
+def check_spgemm_knob_keys(be):
+    """kkamd_set_default: every removed SpGEMM switch is an unknown key now (KKAMD_ERR_INVALID_ARG, at either setting), and every knob
+    the exact-value cases set is still accepted"""
+    for key in REMOVED_SPGEMM_KNOBS:
+        for value in (0, 1, 2):
+            status = be.lib.kkamd_set_default(key.encode(), value)
+            assert status == kk._capi.ERR_INVALID_ARG, (key, value, status)
+            assert "unknown key" in be.lib.kkamd_last_error().decode(errors="replace"), key
+    for key, value in KNOB_DEFAULTS.items():
+        kk._capi.check(be.lib, be.lib.kkamd_set_default(key.encode(), value))
 
 
 class ProductsOf:

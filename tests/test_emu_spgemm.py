@@ -369,3 +369,8 @@ def test_spgemm_options_act_or_raise(be, capfd):
     out = capfd.readouterr().out
     assert "kkamd spgemm symbolic" in out and "compression kept" in out and "kkamd spgemm numeric (SPGEMM_KK)" in out, out
     assert "hint team_work_size = 256 recorded" in out, out
+
+
+def test_spgemm_removed_knobs_are_unknown_keys(be):
+    """kkamd_set_default answers KKAMD_ERR_INVALID_ARG for every removed SpGEMM switch and still accepts every key of KNOB_DEFAULTS"""
+    pc.check_spgemm_knob_keys(be)

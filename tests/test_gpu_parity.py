@@ -979,6 +979,11 @@ def test_spgemm_options_act_or_are_recorded(be, capfd):
     assert "hint team_work_size = 256 recorded" in out, out
 
 
+def test_spgemm_removed_knobs_are_unknown_keys(be):
+    """kkamd_set_default on the HIP build: the removed SpGEMM switches are unknown keys, the keys of KNOB_DEFAULTS are accepted"""
+    pc.check_spgemm_knob_keys(be)
+
+
 def test_fuzz_slice(be):
     """a 60-second slice of the randomised sweep (tests/fuzz_cases.py; tools/fuzz_gpu.py runs it for minutes): every kind of case at
     least once -- SpGEMM skewed / R-MAT with compression and dense-accumulator options / unsorted / long rows, SpMV on irregular
