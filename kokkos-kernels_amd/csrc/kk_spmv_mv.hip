@@ -236,11 +236,13 @@ __global__ __launch_bounds__(kBlock) void spmv_mv_long_kernel(const int32_t* __r
   const int64_t b = (int64_t)row_map[row], end = (int64_t)row_map[row + 1];
   YT acc = YT(0);
   for (int64_t a = b + e; a < end; a += 4 * (kBlock / 16)) {          // four independent entries per lane and step
-    YT v[4]; int32_t c[4];
+    YT v[4], x[4]; int32_t c[4]; bool ok[4];
     KK_UNROLL
-    for (int u = 0; u < 4; ++u) { const int64_t i = a + u * (kBlock / 16); const bool ok = i < end; c[u] = ok ? entries[i] : entries[b]; v[u] = ok ? (YT)values[i] : YT(0); }
+    for (int u = 0; u < 4; ++u) { const int64_t i = a + u * (kBlock / 16); ok[u] = i < end; c[u] = ok[u] ? entries[i] : entries[b]; v[u] = ok[u] ? (YT)values[i] : YT(0); }
     KK_UNROLL
-    for (int u = 0; u < 4; ++u) acc += v[u] * X[(int64_t)c[u] * xs0 + jc * xs1];
+    for (int u = 0; u < 4; ++u) x[u] = X[(int64_t)c[u] * xs0 + jc * xs1];     // the spare slots of the row's last step load from a valid address ...
+    KK_UNROLL
+    for (int u = 0; u < 4; ++u) acc = ok[u] ? acc + v[u] * x[u] : acc;        // ... and add nothing: 0 * X would be NaN where X holds Inf / NaN
   }
   part[threadIdx.x] = acc;
   __syncthreads();

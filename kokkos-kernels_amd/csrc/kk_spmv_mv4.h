@@ -84,7 +84,8 @@ __global__ __launch_bounds__(kBlock) void mv4_rows_kernel(int64_t n_list, const 
     for (int q = 0; q < 16; ++q) {
       const int32_t col = __shfl(my_col, q, 16);
       const double v    = __shfl(my_val, q, 16);
-      acc += v * X[(int64_t)col * xs0 + jc * xs1];
+      const double x    = X[(int64_t)col * xs0 + jc * xs1];       // past the row's end: row 0 of X, a valid address, loaded all the same ...
+      acc = (a + q < e) ? acc + v * x : acc;                       // ... and nothing added: 0 * X would be NaN where X holds Inf / NaN
     }
   }
   if (!live || j >= ncv) return;

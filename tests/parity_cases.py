@@ -1862,11 +1862,11 @@ def check_mv_route_matrix(be, light=False, log=None):
     def ab():
         return ALPHA_BETA[cyc[0] % len(ALPHA_BETA)]
 
-    def run(route, A0, nvec, vt, yt, off, algo, knobs=None, mode="N", lay=None, max_val=1.0, expect=None, seed=0, ab_=None):
+    def run(route, A0, nvec, vt, yt, off, algo, knobs=None, mode="N", lay=None, max_val=1.0, expect=None, seed=0, ab_=None, x_special=None):
         xo, yo, view = lay or layout()
         alpha, beta = ab_ or ab()
         h = check_spmv_mv(be, A0, nvec, mode, alpha, beta, xo, yo, algo=algo, knobs=knobs, max_val=max_val, nans=(beta == 0.0),
-                          offset_dtype=off, value_dtype=vt, vec_dtype=yt, view=view, seed=seed + nvec)
+                          offset_dtype=off, value_dtype=vt, vec_dtype=yt, view=view, seed=seed + nvec, x_special=x_special)
         got = {}
         for k_, want in (expect or {}).items():
             got[k_] = h.query(k_)
@@ -1911,12 +1911,16 @@ def check_mv_route_matrix(be, light=False, log=None):
                     seen.add((Lw, win, nt))
     want = {(L, w, nt) for L in (1, 2, 4) for w in (256, 512, 1024) for nt in (0, 1)}
     assert light or seen == want, sorted(want - seen)
-    # 3. the long-row kernel (rows above the threshold, a workgroup each) after the gather kernel
+    # 3. the long-row kernel (rows above the threshold, a workgroup each) after the gather kernel; Inf in X at the first column of every long
+    # row, where the spare slots of a row's last step of 64 entries load from (the lengths are 56, 28, 1 and 16 modulo 64)
     H = hub_matrix(1500, 5000, 6, {5: 3000, 17: 1500, 700: 1025, 1499: 2000, 40: 1024}, seed=3)
+    first = {int(H.entries[H.row_map[r]]): np.inf for r in (5, 17, 700, 1499)}
     for ni, nvec in enumerate((2, 5, 16, 17, 33) if not light else (5, 17)):
         for ti, (vt, yt) in enumerate(tps):
-            run("long rows", H, nvec, vt, yt, offs[(ni + ti) % 2], "SPMV_DEFAULT", knobs={"mv6": 0, "mv_long_T": 1024}, max_val=50.0,
-                expect={"mv_long_rows": 4, "mv6_chunks": 0})
+            lay3 = layout(); ab3 = ab()
+            for xsp in (None, first):                          # finite sums of every long row, then Inf (same layout, alpha, beta)
+                run("long rows" + (", Inf in X" if xsp else ""), H, nvec, vt, yt, offs[(ni + ti) % 2], "SPMV_DEFAULT", knobs={"mv6": 0, "mv_long_T": 1024},
+                    max_val=50.0, expect={"mv_long_rows": 4, "mv6_chunks": 0}, x_special=xsp, lay=lay3, ab_=ab3)
     # 4. mv3: LDS-staged X tiles (fp64 vectors only: fp32 vectors fall back to the gather kernel with the tile queries at 0)
     M3 = mv3_cases()[0][1]
     for nvec in ((8, 16) if not light else (8,)):
@@ -2043,3 +2047,542 @@ def check_unsupported_pair_leaves_y(be):
                 kk.spmv("N", alpha, A, _to_dev_2d(be, np.ones((40, 3), np.float32)), 0.5, Y)
             assert ei.value.status == kk._capi.ERR_UNSUPPORTED
             assert np.array_equal(be.to_numpy(y), y0) and np.array_equal(_to_host_2d(be, Y), Y0)
+
+
+# ------------------------------------------------------------------------------------------- SpMV: values, exactly
+# check_spmv / check_spmv_mv / check_spmv_struct compare with the oracle under the reference's absolute bound (10 eps times the LONGEST row's
+# worth of products) on non-negative inputs.  The checks below compare y = beta y0 + alpha op(A) x with a plain numpy reference of their own
+# (spmv_by_products, long-double sums of the expanded products): with `==` where the inputs make every partial sum, in any order, exactly
+# representable (signed values, sums that cancel, Inf / NaN / stored zeros in x and in A.values, values replaced on a live handle), and within
+# the per-entry bound of any order of summation where they do not (mode "bound").  Every case proves its route by plan queries, and a table of
+# routes must have been proved from end to end (RouteCoverage).
+SPMV_ALPHAS = (1.0, -1.0, 2.0, -2.0, 0.5, -0.5, 3.0)
+
+
+def spmv_by_products(A0, values, X, mode, alpha, beta, Y0, shortcut=True):
+    """Y = beta Y0 + alpha op(A) X by its definition, in np.longdouble, independent of the oracle: every product a(i, j) x(j) expanded, the
+    products of an output entry added up, alpha times the sum, then + beta Y0 when beta != 0 (Y0 is not read otherwise).  alpha == 0 or a
+    matrix without entries or rows or columns: beta Y0 (zero for beta == 0), whatever A and X hold -- KokkosSparse_spmv.hpp:145.  Rows may be
+    unsorted and hold a column several times.  `values` replaces A0.values; X and Y0 rank 1 or rank 2.  0 * Inf and Inf - Inf are NaN by the
+    IEEE rules.  shortcut=False: alpha == 0 is no special case (0 * Inf is NaN), as in the reference's spmv_struct, which has no such shortcut.
+    Returns (Y, n, S): per output row the number of products n, per entry of Y the sum of |a x| S (both before alpha)."""
+    assert np.finfo(np.longdouble).nmant > np.finfo(np.float64).nmant, "np.longdouble is no wider than float64 here"
+    ld = np.longdouble
+    trans = mode in "TH"
+    nin, nout = (A0.nrows, A0.ncols) if trans else (A0.ncols, A0.nrows)
+    X2 = np.asarray(X, dtype=ld).reshape(nin, -1)
+    Y2 = np.asarray(Y0, dtype=ld).reshape(nout, -1)
+    k = X2.shape[1]
+    row_of = np.repeat(np.arange(A0.nrows, dtype=np.int64), np.diff(A0.row_map))
+    out_i, in_i = (A0.entries.astype(np.int64), row_of) if trans else (row_of, A0.entries.astype(np.int64))
+    n = np.bincount(out_i, minlength=nout).astype(np.int64) if A0.nnz else np.zeros(nout, dtype=np.int64)
+    sums = np.zeros((nout, k), dtype=ld); S = np.zeros((nout, k), dtype=ld)
+    with np.errstate(all="ignore"):
+        if A0.nnz and nout and nin:
+            order = np.argsort(out_i, kind="stable")
+            prod = np.asarray(values, dtype=ld)[order, None] * X2[in_i[order]]
+            first = np.flatnonzero(np.concatenate([[True], out_i[order][1:] != out_i[order][:-1]]))
+            rows = out_i[order][first]
+            sums[rows] = np.add.reduceat(prod, first, axis=0)
+            S[rows] = np.add.reduceat(np.abs(prod), first, axis=0)
+        if (alpha == 0 and shortcut) or A0.nnz == 0 or nout == 0 or nin == 0:
+            Y = ld(beta) * Y2 if beta != 0 else np.zeros((nout, k), dtype=ld)
+        else:
+            Y = ld(alpha) * sums
+            if beta != 0:
+                Y = Y + ld(beta) * Y2
+    shape = np.shape(Y0)
+    return Y.reshape(shape), n, S.reshape(shape)
+
+
+def spmv_n_max(A0, mode):
+    """the most products that meet in one entry of y: the longest row (modes N / C), the most-populated column (modes T / H)"""
+    if not A0.nnz: return 0
+    return int(np.bincount(A0.entries, minlength=A0.ncols).max()) if mode in "TH" else int(np.diff(A0.row_map).max())
+
+
+def spmv_value_bits(n_max, vec_dtype, value_dtype=None):
+    """b: values, x and y0 are signed integers below 2^b times a fixed power of two.  A product has at most 2 b bits, a sum of at most n_max
+    of them 2 b + ceil(log2(n_max + 1)); four more bits cover alpha in {+-1, +-2, +-0.5, 3} and the addition of beta y0.  While the total is at
+    most P, the precision of the vector type (which the kernels accumulate in), every partial sum in any order, fused or not, is exactly
+    representable.  At most 20; fp32 VALUES at most 10 (they must be representable whatever the vector type)."""
+    b = min(20, (P_BITS[np.dtype(vec_dtype)] - 4 - int(math.ceil(math.log2(n_max + 1)))) // 2)
+    if value_dtype is not None and np.dtype(value_dtype) == np.float32:
+        b = min(b, 10)
+    return b
+
+
+def cancelling_values(rng, A0, xr, bc):
+    """values for mode "cancelling": xr holds +-2^k only, so v' = -v xr[c] / xr[c'] is exact.  Inside every row the entries pair up,
+    v[2i+1] = -v[2i] xr[c(2i)] / xr[c(2i+1)]: each pair adds up to exactly zero from two large terms.  EVEN rows of two or more entries sum
+    to exactly 0 (an odd length closes with a triple p - p/2 - p/2); ODD rows keep exactly one product (the unpaired last entry, or a last
+    pair p - 2p).  Returns (values, rows whose sum is exactly zero although they hold two or more products)."""
+    lens = np.diff(A0.row_map)
+    row = np.repeat(np.arange(A0.nrows, dtype=np.int64), lens)
+    within = np.arange(A0.nnz, dtype=np.int64) - A0.row_map[:-1][row]
+    v = exact_values(rng, A0.nnz, bc)
+    ent = A0.entries
+    odd = np.flatnonzero(within % 2 == 1)
+    v[odd] = -v[odd - 1] * xr[ent[odd - 1]] / xr[ent[odd]]
+    rows = np.arange(A0.nrows)
+    tri = rows[(rows % 2 == 0) & (lens % 2 == 1) & (lens >= 3)]           # even row, odd length: the last three entries
+    a = A0.row_map[tri + 1] - 3
+    v[a] *= 2.0
+    p = v[a] * xr[ent[a]]
+    v[a + 1] = -(p / 2) / xr[ent[a + 1]]; v[a + 2] = -(p / 2) / xr[ent[a + 2]]
+    two = rows[(rows % 2 == 1) & (lens % 2 == 0) & (lens >= 2)]           # odd row, even length: the last pair leaves -p
+    a = A0.row_map[two + 1] - 2
+    v[a + 1] = -2.0 * v[a] * xr[ent[a]] / xr[ent[a + 1]]
+    return v, (rows % 2 == 0) & (lens >= 2)
+
+
+class RouteCoverage:
+    """which (route, offset type) of a table a set of cases has PROVED (plan queries held) in which mode, and the largest error / bound seen"""
+
+    def __init__(self, routes):
+        self.proved = {r: set() for r in routes}
+        self.ratio = {r: 0.0 for r in routes}
+
+    def add(self, route, how, ratio=0.0):
+        self.proved[route].add(how)
+        self.ratio[route] = max(self.ratio[route], ratio)
+
+    def report(self):
+        return "\n".join("%-72s proved in %-12s largest error / bound %.3f" % (" / ".join(r) if isinstance(r, tuple) else r, ",".join(sorted(m)) or "-- nothing --", self.ratio[r]) for r, m in self.proved.items())
+
+    def assert_complete(self, what):
+        missing = [r for r, m in self.proved.items() if not m]
+        assert not missing, "%s: no case proved the routes %r" % (what, missing)
+
+
+def _x_targets(A0, mode, rows, extra=()):
+    """positions of x that the kernels' clamped loads aim at: column 0, the last column, the first and last column of the longest and of a middle
+    row (of `rows`, the rows the route under proof computes), a column no row references, and for modes T / H (x runs over the rows) the x of an
+    empty row, the first and the last row"""
+    lens = np.diff(A0.row_map)
+    cand = np.flatnonzero(lens > 0) if rows is None else np.asarray([r for r in rows if lens[r] > 0])
+    longest = int(cand[np.argmax(lens[cand])]); mid = int(cand[len(cand) // 2])
+    if mode in "TH":
+        pos = [0, A0.nrows - 1, longest, mid]
+        empty = np.flatnonzero(lens == 0)
+        if empty.size: pos.append(int(empty[empty.size // 2]))
+    else:
+        pos = [0, A0.ncols - 1]
+        for r in (longest, mid):
+            pos += [int(A0.entries[A0.row_map[r]]), int(A0.entries[A0.row_map[r + 1] - 1])]
+        unused = np.flatnonzero(np.bincount(A0.entries, minlength=A0.ncols) == 0)
+        if unused.size: pos.append(int(unused[unused.size // 2]))
+    out = []
+    for p in list(pos) + [int(e) for e in extra]:
+        if p not in out: out.append(p)
+    return out
+
+
+def _classes(Y, rows):
+    Yr = np.asarray(Y, dtype=np.float64).reshape(Y.shape[0], -1)
+    if rows is not None: Yr = Yr[np.asarray(rows)]
+    nan = np.isnan(Yr).any(axis=1); inf = np.isinf(Yr).any(axis=1) & ~nan
+    return bool(inf.any()), bool(nan.any()), bool((~nan & ~inf & np.isfinite(Yr).all(axis=1)).any())
+
+
+def check_spmv_exact(be, A0, how="signed", mode="N", nvec=None, algo=None, knobs=None, proof=None, value_dtype=None, vec_dtype=np.float64,
+                     offset_dtype=np.int32, x_order="C", y_order="C", view=None, struct=None, route_rows=None, x_extra=(), zero_at=(),
+                     seed=0, name=""):
+    """y = beta y0 + alpha op(A) x on the STRUCTURE of A0, with values, x and y0 drawn here, through the same entry points as check_spmv /
+    check_spmv_mv / check_spmv_struct (nvec None: rank 1; struct = (stencil_type, dims): spmv_struct), against spmv_by_products.  An analysed
+    handle is called a second time when beta == 0; `proof` (a function of the handle's query) must hold afterwards.  By `how`:
+      signed      values integers of b bits (spmv_value_bits) times 2^-4, x times 2^-3, y0 times 2^-2, alpha and beta from SPMV_ALPHAS, beta = 0
+                  over a y full of NaN: got == expected, entry by entry (signed zeros are not told apart)
+      cancelling  (modes N / C) x = +-2^k, entries paired so that even rows sum to exactly 0 from large terms and odd rows keep one product
+                  (cancelling_values): `==`, the zero rows are 0 (beta = 0), both parities among the rows the route computes
+      special     on signed values: +Inf in x at the positions the clamped loads aim at (_x_targets); then 0, +Inf, -Inf, NaN in turn there;
+                  then those four in A.values at special_positions, written in place under a live handle; then finite values written back in
+                  place -- handle.values_changed() under values_tracking 1 for 32-bit offsets, exact tracking (the default) for 64-bit ones --
+                  and `==` again; then alpha = 0 over the specials in A and x: beta y0 (spmv_struct: beta y0 + 0 * sum, as the reference's, which
+                  has no shortcut).  NaN where the expectation is NaN, the same infinity
+                  where it is one, `==` elsewhere; every step's expectation holds an Inf row, a NaN row (not the first step: one sign of Inf
+                  alone) and a finite row among the rows the route computes
+      bound       values uniform in (-50, 50) rounded to the value type, x and y0 in (-1, 1): |got - ref| <= gamma_(n+2) (|alpha| S + |beta y0|)
+                  per entry, gamma_m = m u / (1 - m u), u the unit roundoff of the vector type, n and S the entry's products and sum |a x|
+                  (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., section 3.1: n products, n - 1 additions, alpha, beta y0)
+    route_rows: the rows the route under proof computes when that is not all of them (the long rows of spmv_mv_long_kernel).  x_extra: more
+    positions of x for the special values.  zero_at: positions of A.values that hold a stored 0.0 in every draw and are left out of the
+    reference (the entries spmv_struct's interior rows do not read).  Returns (handle, largest error / bound)."""
+    vdt = np.dtype(vec_dtype); adt = np.dtype(value_dtype) if value_dtype is not None else np.dtype(np.float64)
+    rng = np.random.default_rng([seed, 23])
+    trans = mode in "TH"
+    assert not (how == "cancelling" and trans)
+    nin, nout = (A0.nrows, A0.ncols) if trans else (A0.ncols, A0.nrows)
+    k = 1 if nvec is None else nvec
+    shape = lambda n_: (n_,) if nvec is None else (n_, nvec)
+    zero_at = np.asarray(zero_at, dtype=np.int64)
+    keep = np.ones(A0.nnz, dtype=bool); keep[zero_at] = False
+    if zero_at.size:                                        # the reference's matrix: A0 without the entries that are never read
+        row = np.repeat(np.arange(A0.nrows, dtype=np.int64), np.diff(A0.row_map))[keep]
+        rmr = np.zeros(A0.nrows + 1, dtype=np.int64); np.cumsum(np.bincount(row, minlength=A0.nrows), out=rmr[1:])
+        Ar = oracle.Crs(A0.nrows, A0.ncols, rmr, A0.entries[keep], np.zeros(int(keep.sum())))
+    else:
+        Ar = A0
+    b = spmv_value_bits(spmv_n_max(Ar, mode), vdt, adt)
+    assert b >= 2, "%s: %d products meet in one entry: %d-bit values cannot tell a rounding apart" % (name, spmv_n_max(Ar, mode), b)
+    rows_all = route_rows is None
+    lens = np.diff(Ar.row_map)
+
+    def full(vr):                                           # values of the library's matrix from those of the reference's
+        v = np.zeros(A0.nnz); v[keep] = vr
+        return v
+
+    def draw_xy():
+        x = (exact_values(rng, nin * k, b) * 2.0).reshape(shape(nin))
+        y0 = (exact_values(rng, nout * k, b) * 4.0).reshape(shape(nout))
+        return x, y0
+
+    def scalars(i):
+        alpha = SPMV_ALPHAS[int(rng.integers(len(SPMV_ALPHAS)))]
+        beta = 0.0 if i % 2 == 0 else SPMV_ALPHAS[int(rng.integers(len(SPMV_ALPHAS)))]
+        return alpha, beta
+
+    A = dev(be, _with_values(A0, np.zeros(A0.nnz)), offset_dtype, adt)
+    h = None
+    if algo is not None and struct is None:
+        h = kk.SPMVHandle(algo)
+        for k_, v_ in (knobs or {}).items(): h.set(k_, v_)
+        if how == "special" and offset_dtype == np.int32: h.set("values_tracking", 1)
+
+    def set_values(vr, notify):
+        A.values[:] = be.from_numpy(full(vr).astype(adt))
+        if notify and h is not None and offset_dtype == np.int32: h.values_changed()
+
+    def call(alpha, beta, x, y0):
+        xh = np.asarray(x, order=x_order).astype(vdt, order="K")
+        yh = np.full(shape(nout), np.nan, dtype=vdt, order=y_order) if beta == 0.0 else np.asarray(y0, order=y_order).astype(vdt, order="K")
+        if nvec is None:
+            xd, yd = be.from_numpy(xh), be.from_numpy(yh)
+        elif view is not None:
+            xd, xpd, xp0, xwin = _window_2d(be, xh, x_order, view_spec(view, nvec, vdt.itemsize))
+            yd, ypd, yp0, ywin = _window_2d(be, yh, y_order, view_spec(view, nvec, vdt.itemsize), fill_bits=SENTINEL_BITS[vdt])
+        else:
+            xd, yd = _to_dev_2d(be, xh), _to_dev_2d(be, yh)
+        if struct is not None:
+            kk.spmv_struct(mode, struct[0], struct[1], alpha, A, xd, beta, yd)
+        elif h is None:
+            kk.spmv(mode, alpha, A, xd, beta, yd)
+        else:
+            kk.spmv(h, mode, alpha, A, xd, beta, yd)
+            if beta == 0.0: kk.spmv(h, mode, alpha, A, xd, beta, yd)                   # handle reuse
+        if nvec is None:
+            return be.to_numpy(yd).astype(np.float64)
+        if view is not None:
+            Yp = _to_host_2d(be, ypd)
+            assert_outside_unchanged(yp0, Yp, ywin, "Y")
+            assert_outside_unchanged(xp0, _to_host_2d(be, xpd), (slice(0, 0), slice(0, 0)), "X")
+            return Yp[ywin].astype(np.float64)
+        return _to_host_2d(be, yd).astype(np.float64)
+
+    def compare(got, Y, n, what):
+        with np.errstate(all="ignore"):
+            ref = np.asarray(Y, dtype=np.float64)
+            fin = np.isfinite(ref)
+            assert (ref[fin] == Y[fin]).all() and (ref[fin].astype(vdt).astype(np.float64) == ref[fin]).all(), \
+                "%s %s: the reference's sums are not representable in %s (the case's b is wrong)" % (name, what, vdt.name)
+        nan = np.isnan(ref)
+        bad = (np.isnan(got) != nan) | (~nan & (got != ref))
+        if bad.any():
+            at = tuple(int(i) for i in np.argwhere(bad)[0])
+            raise AssertionError("%s %s: %d entries of y differ, first at %s (%d products): %r, reference %r" % (
+                name, what, int(bad.sum()), at, int(n[at[0]]), got[at], ref[at]))
+
+    def representable(*arrs):
+        for a_, dt in arrs:
+            assert np.array_equal(a_.astype(dt).astype(np.float64), a_, equal_nan=True), name + ": an input is not representable in " + np.dtype(dt).name
+
+    ratio = 0.0
+    if how == "signed":
+        vr = exact_values(rng, Ar.nnz, b)
+        set_values(vr, False)
+        for i in range(2):
+            x, y0 = draw_xy(); alpha, beta = scalars(i)
+            representable((vr, adt), (x, vdt), (y0, vdt))
+            Y, n, S = spmv_by_products(Ar, vr, x, mode, alpha, beta, y0)
+            compare(call(alpha, beta, x, y0), Y, n, "signed alpha %g beta %g" % (alpha, beta))
+    elif how == "cancelling":
+        assert b >= 4, "%s: %d-bit values leave nothing after the three bits the pairs cost" % (name, b)
+        xr = np.where(rng.random(nin) < 0.5, -1.0, 1.0) * 2.0 ** rng.integers(0, 4, size=nin)
+        d = np.where(rng.random(k) < 0.5, -1.0, 1.0) * 2.0 ** rng.integers(0, 2, size=k)       # rank 2: every column of X is xr times +-1 or +-2
+        x = xr if nvec is None else np.outer(xr, d)
+        vr, zero_rows = cancelling_values(rng, Ar, xr, b - 3)
+        sel = np.arange(Ar.nrows) if rows_all else np.asarray(route_rows)
+        kept = (sel % 2 == 1) & (lens[sel] >= 1)
+        assert zero_rows[sel].any() and kept.any(), "%s: the rows of the route hold %d cancelling and %d product-keeping rows" % (name, int(zero_rows[sel].sum()), int(kept.sum()))
+        set_values(vr, False)
+        for i in range(2):
+            _, y0 = draw_xy(); alpha, beta = scalars(i)
+            representable((vr, adt), (x, vdt), (y0, vdt))
+            Y, n, S = spmv_by_products(Ar, vr, x, mode, alpha, beta, y0)
+            if beta == 0.0:
+                Yr = np.asarray(Y, dtype=np.float64).reshape(nout, -1)
+                assert (Yr[zero_rows] == 0).all() and (Yr[sel[kept]] != 0).all() and (S.reshape(nout, -1)[zero_rows] > 0).all(), name + ": the cancelling rows do not cancel in the reference"
+            got = call(alpha, beta, x, y0)
+            compare(got, Y, n, "cancelling alpha %g beta %g" % (alpha, beta))
+            if beta == 0.0: assert (got.reshape(nout, -1)[zero_rows] == 0).all()
+    elif how == "special":
+        vr = exact_values(rng, Ar.nnz, b)
+        targets = _x_targets(Ar, mode, route_rows, x_extra)
+        hit = np.zeros(nin, dtype=bool); hit[targets] = True
+        # a row of the route that meets the fewest targets (at least one) gets positive values there: + Inf and not Inf - Inf
+        row_of = np.repeat(np.arange(Ar.nrows, dtype=np.int64), lens)
+        if not trans:
+            hits = np.bincount(row_of[hit[Ar.entries]], minlength=Ar.nrows)
+            cand = np.flatnonzero(hits > 0) if rows_all else np.asarray([r for r in route_rows if hits[r] > 0])
+            assert cand.size, name + ": no row of the route references a target column"
+            ragged = cand[lens[cand] % 64 != 0]               # a row whose last step of 64 entries (the long-row kernel's) has spare slots, if there is one
+            cand = ragged if ragged.size else cand
+            r_inf = int(cand[np.argmin(hits[cand])])
+            seg = slice(int(Ar.row_map[r_inf]), int(Ar.row_map[r_inf + 1]))
+            vr[seg] = np.where(hit[Ar.entries[seg]], np.abs(vr[seg]), vr[seg])
+        set_values(vr, False)
+        x, y0 = draw_xy()
+        sel = None if rows_all else (np.asarray(route_rows) if not trans else None)
+        col0 = lambda a_: a_ if nvec is None else a_[:, 0]
+        def run(xs, vs, alpha, beta, what, need_nan=True, classes=True, shortcut=True):
+            Y, n, S = spmv_by_products(Ar, vs, xs, mode, alpha, beta, y0, shortcut)
+            if classes:
+                has = _classes(Y, sel)
+                assert has[0] and (has[1] or not need_nan) and has[2], "%s %s: the expectation holds (Inf, NaN, finite) rows: %r" % (name, what, has)
+            compare(call(alpha, beta, xs, y0), Y, n, what)
+        # 1. one sign of Inf in x
+        xs = x.copy(); xs[targets] = np.inf
+        alpha, beta = scalars(0)
+        run(xs, vr, abs(alpha), beta, "special: +Inf in x", need_nan=False)
+        # 2. 0, +Inf, -Inf, NaN in turn; the rotation is the first that shows the three classes (found on the reference alone)
+        for rot in range(4):
+            xs = x.copy()
+            xs[targets] = (np.array(SPECIALS)[(np.arange(len(targets)) + rot) % 4])[:, None] if nvec is not None else np.array(SPECIALS)[(np.arange(len(targets)) + rot) % 4]
+            if all(_classes(spmv_by_products(Ar, vr, col0(xs), mode, 1.0, 0.0, col0(y0))[0], sel)): break      # (whole rows of X are special: one column tells)
+        alpha, beta = scalars(1)
+        run(xs, vr, alpha, beta, "special: 0 / Inf / -Inf / NaN in x")
+        # 3. the four in A.values, in place under the live handle
+        if rows_all or trans:
+            pos = special_positions(rng, Ar, extra=min(48, 2 + Ar.nnz // 64))
+        else:                                                   # the first entry of three rows of the route (the others stay finite), both ends of a row outside it
+            rr = np.asarray(route_rows)[:3]
+            other = int(np.flatnonzero((lens > 0) & ~np.isin(np.arange(Ar.nrows), route_rows))[0])
+            pos = np.concatenate([Ar.row_map[rr], [Ar.row_map[other], Ar.row_map[other + 1] - 1]])
+        for rot in range(4):
+            vs = vr.copy(); vs[pos] = np.array(SPECIALS)[(np.arange(len(pos)) + rot) % 4]
+            if all(_classes(spmv_by_products(Ar, vs, col0(x), mode, 1.0, 0.0, col0(y0))[0], sel)): break
+        set_values(vs, True)
+        alpha, beta = scalars(0)
+        run(x, vs, alpha, beta, "special: 0 / Inf / -Inf / NaN in A.values")
+        # 4. alpha = 0 over specials in A and in x: beta y0 (0 over NaN for beta = 0).  The reference's spmv_struct has no such shortcut (its
+        # non-transposed rows compute beta y0 + 0 * sum: NaN where the sum is Inf or NaN), and neither has the library's
+        for beta in (0.0, -2.0):
+            run(xs, vs, 0.0, beta, "special: alpha 0 over specials", classes=False, shortcut=struct is None or trans)
+        # 5. finite values written back in place: nothing non-finite may survive in a copy the plan keeps
+        vr2 = exact_values(rng, Ar.nnz, b)
+        set_values(vr2, True)
+        for i in range(2):
+            alpha, beta = scalars(i)
+            run(x, vr2, alpha, beta, "special: finite values written back (alpha %g beta %g)" % (alpha, beta), classes=False)
+    elif how == "bound":
+        vr = rng.uniform(-50, 50, Ar.nnz).astype(adt).astype(np.float64)
+        set_values(vr, False)
+        u = U_ROUND[vdt]
+        for i in range(2):
+            x = rng.uniform(-1, 1, shape(nin)).astype(vdt).astype(np.float64); y0 = rng.uniform(-1, 1, shape(nout)).astype(vdt).astype(np.float64)
+            alpha, beta = scalars(i)
+            Y, n, S = spmv_by_products(Ar, vr, x, mode, alpha, beta, y0)
+            got = call(alpha, beta, x, y0)
+            m = (n + 2).astype(np.longdouble).reshape((nout,) + (1,) * (got.ndim - 1))
+            bound = m * u / (1 - m * u) * (abs(alpha) * S + (np.abs(beta * y0) if beta != 0 else 0))
+            err = np.abs(got.astype(np.longdouble) - Y)
+            bad = ~(err <= bound)
+            if bad.any():
+                at = tuple(int(i_) for i_ in np.argwhere(bad)[0])
+                raise AssertionError("%s bound alpha %g beta %g: %d entries outside gamma_(n+2) (|alpha| S + |beta y0|), first at %s (%d products): %r, reference %r, bound %g" % (
+                    name, alpha, beta, int(bad.sum()), at, int(n[at[0]]), got[at], float(Y[at]), float(bound[at])))
+            nz = bound > 0
+            if nz.any(): ratio = max(ratio, float((err[nz] / bound[nz]).max()))
+    else:
+        raise ValueError(how)
+    if proof is not None:
+        assert h is not None and proof(h.query), "%s: the plan queries do not prove the route: %s" % (name, {k_: h.query(k_) for k_ in (
+            "tile", "tiles", "plain_tiles", "code_tiles", "staged_tiles", "pattern_tiles", "pattern_direct", "march_workgroups", "colslab", "colslab_deterministic",
+            "transpose_cached", "mv_tiles", "mv_staged_tiles", "mv_long_rows", "mv4_workgroups", "mv4_other_rows", "mv5_tiles", "mv6_chunks")})
+    return h, ratio
+
+
+def plain_tile_matrix(npt, exact, seed=0):
+    """rows for the planned kernel's plain tiles of 256 * npt entries: a row of 2 * tile - 100 entries from entry 185 on, which spans three
+    tiles (its middle tile holds nothing else: the fixup kernel adds the carries up; 3996 entries at tiles of 2048 still leave fp32 sums
+    four bits), rows that end exactly at a tile's end, empty rows, and a last tile that is full (exact) or ragged;
+    unsorted rows with duplicate columns"""
+    tile = 256 * npt
+    lens = [5] * 37 + [2 * tile - 100] + [3, 0, 7] * 40 + [tile - 11] + [1] * 20
+    lens.append((-sum(lens)) % tile if exact else ((-sum(lens)) % tile + 13) % tile or 13)
+    lens = np.asarray(lens, dtype=np.int64)
+    rm = np.zeros(lens.size + 1, dtype=np.int64); np.cumsum(lens, out=rm[1:])
+    assert (rm[-1] % tile == 0) == exact
+    rng = np.random.default_rng([seed, npt])
+    return oracle.Crs(lens.size, 2 * tile + 77, rm, rng.integers(0, 2 * tile + 77, size=rm[-1]).astype(np.int32), np.ones(rm[-1]))
+
+
+def values_hub_matrix(seed=3):
+    """short rows and hubs whose lengths are 1, 0 and other residues modulo 64 (the long-row kernel walks a row 64 entries at a step), one of
+    them exactly at the threshold 1024 (it stays with the gather kernel); columns spread over 30000 so that a long row misses most targets"""
+    return hub_matrix(600, 30000, 5, {5: 1089, 17: 1152, 300: 1030, 599: 1100, 40: 1024}, seed=seed)
+
+
+def struct_extra_entry(dims, stencil_type):
+    """(matrix, positions of its extra entries): a stencil matrix whose interior rows r each hold one more entry at their end (a stored 0.0 that
+    spmv_struct's interior kernel does not read: the rows of that chunk go through row_map instead of the contiguous block of values)"""
+    A0 = struct_matrix(dims, stencil_type)
+    rm = A0.row_map.copy(); ent = A0.entries; val = A0.values
+    at = []
+    for r in (dims[0] + 7, dims[0] + 100):
+        at.append(int(rm[r + 1]))
+        ent = np.insert(ent, rm[r + 1], ent[rm[r + 1] - 1]); val = np.insert(val, rm[r + 1], 0.0); rm[r + 1:] += 1
+    return oracle.Crs(A0.nrows, A0.ncols, rm, ent.astype(np.int32), val), at
+
+
+F64_PAIRS = ((None, np.float64), (np.float32, np.float64))
+
+
+def spmv_value_routes(kind, light=False):
+    """the table of routes: dicts of name, A0, and what check_spmv_exact takes (algo, knobs, proof, mode, nvec, layouts, struct, ...).
+    pairs: the (value, vector) type pairs the route accepts; proof32: the proof when the vectors are fp32 and the route falls back."""
+    R = []
+    def add(name, A0, algo=None, knobs=None, proof=None, modes="N", pairs=TYPE_PAIRS, **kw):
+        R.append(dict(name=name, A0=A0, algo=algo, knobs=knobs, proof=proof, modes=modes, pairs=pairs, kw=kw))
+    q_plain = lambda q: q("plain_tiles") == q("tiles") > 0
+    only64 = lambda npt: TYPE_PAIRS[:1] if npt == 4 else TYPE_PAIRS           # tiles of 1024 entries exist for fp64 values only
+    if kind == "rank1":
+        G = oracle.random_crs(300 if light else 1500, 280 if light else 1400, 9, variance=4, seed=41)        # unsorted rows, duplicate columns
+        add("vector kernel (no handle)", G, modes="NC")
+        for lanes in (1, 4, 64):
+            add("vector kernel, FAST_SETUP, %d lanes per row" % lanes, G, "SPMV_FAST_SETUP", {"lanes_per_row": lanes}, lambda q: q("tiles") == 0)
+        for npt in (4, 8, 16):
+            add("plain tiles of %d, ragged last tile" % (256 * npt), plain_tile_matrix(npt, False), "SPMV_DEFAULT", {"nnz_per_thread": npt},
+                lambda q, t=256 * npt: q("tile") == t and q("plain_tiles") == q("tiles") > 3, pairs=only64(npt),
+                # a row through three tiles of 4096 holds more than 4095 entries: three bits in fp32 sums, too few for the cancelling pairs
+                **({"cancel_pairs": F64_PAIRS} if npt == 16 else {}))
+        add("plain tiles of 1024, full last tile", plain_tile_matrix(4, True), "SPMV_DEFAULT", {"nnz_per_thread": 4},
+            lambda q: q("tile") == 1024 and q("plain_tiles") == q("tiles") > 3, pairs=only64(4))
+        add("code tiles", window_code_cases()[1][1], "SPMV_DEFAULT", {"window_codes_min_knnz": 0, "window_codes": 2, "nnz_per_thread": 8},
+            lambda q: q("code_tiles") > 0 and q("staged_tiles") == 0)
+        add("staged-x tiles", oracle.laplace3d("FE", 24, 9, 7) if light else oracle.laplace3d("FE", 64, 20, 9), "SPMV_DEFAULT",
+            {"window_codes_min_knnz": 0, "nnz_per_thread": 8, "pattern_codes": 0}, lambda q: q("staged_tiles") > 0 and q("pattern_tiles") == 0)
+        pcs = {c[0]: c for c in pattern_code_cases()}
+        pats = (("one segment (27-pt)", oracle.laplace3d("FE", 60, 9, 5) if light else pcs["27pt"][1], 8 if light else 16),) + \
+               (() if light else (("several segments (9-pt, perturbed rows)", pcs["9pt-perturbed"][1], 16), ("several segments (5-pt, empty rows)", pcs["5pt-empty-rows"][1], 16)))
+        for what, M, npt in pats:
+            # the matrices whose tiles hold several segments leave more than one tile in a hundred without a record: the library builds their
+            # records through the codes whatever pattern_direct says (it is asked for here), and the records sit beside tiles that read codes
+            several = not what.startswith("one")
+            for direct in ((1,) if several else (1, 0)):
+                add("pattern tiles, %s, %s" % (what, "through codes, beside code tiles" if several else ("straight from the matrix" if direct else "through codes")),
+                    M, "SPMV_DEFAULT", {"window_codes_min_knnz": 0, "nnz_per_thread": npt, "pattern_codes": 2, "pattern_codes_min_knnz": 0, "pattern_direct": direct},
+                    (lambda q: q("pattern_tiles") > 0 and q("code_tiles") > 0 and q("pattern_direct") == 0) if several else
+                    (lambda q, d=direct: q("pattern_tiles") > 0 and q("pattern_direct") == d), pairs=only64(npt))
+        add("mixed tiles", mixed_tile_cases()[1][1], "SPMV_DEFAULT", {"window_codes_min_knnz": 0, "nnz_per_thread": 8, "pattern_codes": 0, "window_codes_min_pct": 10},
+            lambda q: 0 < q("plain_tiles") < q("tiles"))
+        m4 = {c[0]: c[1] for c in mv4_cases()}
+        add("march, every row", m4["7pt clean 33x6x21"], "SPMV_DEFAULT", {"march": 1}, lambda q: q("march_workgroups") > 0 and q("mv4_other_rows") == 0, pairs=F64_PAIRS)
+        add("march, with rows left to the gather rows", m4["7pt + broken rows"], "SPMV_DEFAULT", {"march": 1}, lambda q: q("march_workgroups") > 0 and q("mv4_other_rows") == 4, pairs=F64_PAIRS)
+        S = oracle.random_crs(700 if light else 3000, 3000, 9, variance=4, seed=3)
+        add("column slab, atomic", S, "SPMV_DEFAULT", {"colslab": 2, "colslab_shift": 6}, lambda q: q("colslab") == 1 and q("colslab_deterministic") == 0)
+        add("column slab, deterministic", S, "SPMV_DEFAULT", {"colslab": 4, "colslab_shift": 6}, lambda q: q("colslab") == 1 and q("colslab_deterministic") == 1)
+        for algo in ("SPMV_MERGE_PATH", "SPMV_NATIVE", "SPMV_NATIVE_MERGE_PATH"):
+            add(algo, G, algo, None, q_plain, modes="NC")
+        E = mv6_cases()[4][1]                                                                  # empty rows, a row of 1000, 5000 columns
+        add("transposed, atomics (no handle)", E, modes="TH")
+        add("transposed, atomics (explicit_transpose 0)", E, "SPMV_DEFAULT", {"explicit_transpose": 0}, lambda q: q("transpose_cached") == 0, modes="TH")
+        add("transposed, cached transpose", E, "SPMV_DEFAULT", {"explicit_transpose": 1, "explicit_transpose_min_knnz": 0}, lambda q: q("transpose_cached") == 1, modes="TH")
+    elif kind == "struct":
+        # grids with two or three chunks of interior rows per line; specials on boundary points (_x_targets: the first and the last column) and
+        # on the halo of an interior chunk: the points left and right of the chunk that begins at i = 65
+        for what, dims, st in (("1-D", (300,), 1), ("2-D FD", (140, 6), 1), ("2-D FE", (140, 6), 2), ("3-D FD", (140, 5, 4), 1), ("3-D FE", (140, 5, 4), 2)):
+            line = 0 if len(dims) == 1 else (dims[0] * (2 if len(dims) == 2 else dims[1] + 2))
+            add("spmv_struct %s" % what, struct_matrix(dims, st), struct=(st, dims), x_extra=(line + 64, line + 129), modes="NT" if what == "2-D FE" else "N")
+        A1, at = struct_extra_entry((140, 6), 2)
+        add("spmv_struct 2-D FE, rows with an extra entry", A1, struct=(2, (140, 6)), zero_at=at, x_extra=(2 * 140 + 64, 2 * 140 + 129))
+    elif kind == "rank2":
+        G = oracle.random_crs(300 if light else 1500, 280 if light else 1400, 9, variance=4, seed=41)
+        add("generic (no handle)", G, nvecs=(3, 12), lays=(("F", "C", None), ("C", "C", "odd_start"), ("F", "F", "tall")), modes="NC")
+        M2 = oracle.random_crs(300 if light else 1200, 1100, 10, variance=0, seed=60)
+        none = lambda q: q("mv4_workgroups") == 0 and q("mv5_tiles") == 0 and q("mv6_chunks") == 0 and q("mv_tiles") == 0 and q("mv_long_rows") == 0
+        for nt in (0, 1):
+            add("gather kernel, nt %d" % nt, M2, "SPMV_DEFAULT", {"mv_kernel": 2, "mv_nt": nt}, none, nvecs=(2, 5, 16), lays=(("C", "C", None), ("F", "F", None), ("C", "F", "even_pitch")))
+        H = values_hub_matrix()
+        long_rows = [int(r) for r in np.flatnonzero(np.diff(H.row_map) > 1024)]
+        add("long rows", H, "SPMV_DEFAULT", {"mv6": 0, "mv_long_T": 1024}, lambda q: q("mv_long_rows") == 4 and q("mv6_chunks") == 0, nvecs=(5, 16, 17),
+            lays=(("C", "C", None), ("F", "F", None), ("C", "F", None)), route_rows=long_rows)
+        add("mv3 (LDS-staged X)", oracle.laplace3d("FE", 20, 9, 7) if light else mv3_cases()[0][1], "SPMV_DEFAULT", {"mv_kernel": 3},
+            lambda q: q("mv_staged_tiles") > 0 and q("mv_tiles") > 0, proof32=lambda q: q("mv_staged_tiles") == 0 and q("mv_tiles") == 0, nvecs=(8, 16))
+        cases = mv4_cases()
+        for i in ((0,) if light else (0, 1, 4, 5)):
+            add("mv4 (plane marching) on %s" % cases[i][0], cases[i][1], "SPMV_DEFAULT", None, lambda q: q("mv4_workgroups") > 0, proof32=lambda q: q("mv4_workgroups") == 0,
+                nvecs=(5, 16), lays=(("C", "C", "even_pitch"), ("F", "F", None)))
+        five = mv5_cases()
+        for i in ((0,) if light else (0, 1)):
+            add("mv5 (matrix cores) on %s" % five[i][0], five[i][1], "SPMV_DEFAULT", None, lambda q: q("mv5_tiles") > 0, proof32=lambda q: q("mv5_tiles") == 0, nvecs=(3, 16, 17))
+        E = mv6_cases()[4][1]
+        add("mv6 (nonzero split)", E, "SPMV_DEFAULT", {"mv6": 2}, lambda q, c=-(-E.nnz // 128): q("mv6_chunks") == c, proof32=lambda q: q("mv6_chunks") == 0, nvecs=(2, 5, 16),
+            lays=(("C", "C", "even_pitch"), ("F", "F", None), ("C", "C", None)))
+        T0 = oracle.random_crs(300 if light else 2000, 250 if light else 1600, 9, variance=4, seed=43)
+        add("transposed, atomics (no handle)", T0, nvecs=(3, 16), modes="TH")
+        add("transposed, atomics (explicit_transpose 0)", T0, "SPMV_DEFAULT", {"explicit_transpose": 0}, lambda q: q("transpose_cached") == 0, nvecs=(3, 16), modes="TH")
+        add("transposed, cached transpose", T0, "SPMV_DEFAULT", {"explicit_transpose_min_knnz": 0}, lambda q: q("transpose_cached") == 1, nvecs=(3, 17), modes="TH")
+    else:
+        raise ValueError(kind)
+    return R
+
+
+VALUE_MODES = ("signed", "cancelling", "special", "bound")
+
+
+def check_spmv_values(be, how, kind, light=False, offsets=(np.int32, np.int64)):
+    """every route of spmv_value_routes(kind) in mode `how`: for each offset type of `offsets`, EVERY (value, vector) type pair the route accepts
+    (their kernels are separate instantiations), widths, layouts and transposition modes taking turns with the call, the offset type and the mode
+    (so that the four modes and two offset types between them walk every width of the table on every pair).  The route is proved by its plan
+    queries at every call, and at the end every route must have been proved with every offset type asked for (mode "cancelling" has no
+    transposed form: those routes are left out of its table).  light: one call per route, offset types and type pairs in turn, every route
+    proved once.  A pair that leaves too few bits for the values (spmv_value_bits below 2; below 4 in mode "cancelling", whose pairs cost
+    three) is an error in the table: a route says which pairs it takes in mode "cancelling" where those are fewer (cancel_pairs).
+    A call without a handle and spmv_struct have no plan to query: what they run follows from the call alone (no analysis, a matrix below
+    transient_min_knnz: the vector kernel, the atomic transposed kernel, the generic rank-2 kernel; the structured kernels).  A rank-2 route
+    whose kernel takes fp64 vectors only is called with fp32 vectors too, must say so in its queries (proof32), and that call does not count
+    as proof.  Prints what was proved and, in mode "bound", the largest error / bound per route."""
+    routes = [r for r in spmv_value_routes(kind, light) if not (how == "cancelling" and r["modes"] == "TH")]
+    onames = ["any"] if light else [np.dtype(o).name for o in offsets]
+    cov = RouteCoverage([(r["name"], o) for r in routes for o in onames])
+    need = 4 if how == "cancelling" else 2
+    hk = VALUE_MODES.index(how)
+    for ri, r in enumerate(routes):
+        kw = dict(r["kw"])
+        nvecs = kw.pop("nvecs", (None,)); lays = kw.pop("lays", (("C", "C", None), ("F", "F", None))); proof32 = kw.pop("proof32", None)
+        cancel_pairs = kw.pop("cancel_pairs", None)
+        modes = "N" if how == "cancelling" and r["modes"] == "NT" else r["modes"]
+        pairs = list(cancel_pairs if how == "cancelling" and cancel_pairs is not None else r["pairs"])
+        for vt, yt in pairs:
+            bits = min(spmv_value_bits(spmv_n_max(r["A0"], m_), yt, vt) for m_ in modes)
+            assert bits >= need, "%s: %s leaves %d bits for the values, mode %s needs %d" % (r["name"], _tp_name(vt, yt), bits, how, need)
+        proving = [p_ for p_ in pairs if not (proof32 is not None and nvecs[0] is not None and p_[1] == np.float32)]
+        if light:
+            calls = [((np.int32, np.int64)[(ri + hk) % 2], proving[(ri + hk) % len(proving)])]
+        else:
+            calls = [(off, p_) for off in offsets for p_ in pairs]
+        for ci, (off, (vt, yt)) in enumerate(calls):
+            i = ri + ci + hk + (np.dtype(off).itemsize // 8)
+            nvec = nvecs[i % len(nvecs)]
+            xo, yo, view = lays[(i + i // len(nvecs)) % len(lays)] if nvec is not None else ("C", "C", None)
+            mode = modes[i % len(modes)]
+            fallback = (vt, yt) not in proving
+            proof = proof32 if fallback else r["proof"]
+            tag = "%s [%s, %s, %s, mode %s%s]" % (r["name"], how, np.dtype(off).name, _tp_name(vt, yt), mode, "" if nvec is None else ", %d columns %s%s %s" % (nvec, xo, yo, view or ""))
+            h, ratio = check_spmv_exact(be, r["A0"], how, mode, nvec, r["algo"], r["knobs"], proof, vt, yt, off, xo, yo, view, seed=i, name=tag, **kw)
+            if not fallback:
+                cov.add((r["name"], "any" if light else np.dtype(off).name), how, ratio)
+    print("SpMV values, %s, %s:\n%s" % (kind, how, cov.report()))
+    cov.assert_complete("%s, %s" % (kind, how))
+    return cov

@@ -246,10 +246,16 @@ def test_mv6_nonzero_split(be):
 def test_mv_long_rows(be):
     # rank 2 on a matrix with a few very long rows (R-MAT-like hubs): the wave-private gather kernel leaves rows above 32 x the average
     # length (at least 1024 entries) to spmv_mv_long_kernel (a workgroup per row); every width, both layouts, beta 0 over NaNs and != 0
+    # Inf in X at the first column of every long row: the spare slots of a row's last step of 64 entries load from there and must add nothing
     A0 = pc.hub_matrix(3000, 9000, 6, {5: 7000, 17: 1500, 1234: 1025, 2999: 4000, 40: 1024}, seed=3)
+    first = {int(A0.entries[A0.row_map[r]]): np.inf for r in (5, 17, 1234, 2999, 40)}
     for nvec, xo, yo, alpha, beta in ((16, "C", "C", 1.5, 0.0), (16, "F", "F", 1.0, 0.5), (5, "C", "C", 2.0, -1.0), (33, "C", "F", 1.0, 0.0), (2, "C", "C", 1.0, 1.0)):
         h = pc.check_spmv_mv(be, A0, nvec, "N", alpha, beta, xo, yo, algo="SPMV_DEFAULT", max_val=50.0, nans=(beta == 0.0), knobs={"mv_long_T": 1024, "mv6": 0})
         assert h.query("mv_long_rows") == 4, h.query("mv_long_rows")            # 7000, 1500, 1025, 4000 (1024 itself stays)
+        h = pc.check_spmv_mv(be, A0, nvec, "N", alpha, beta, xo, yo, algo="SPMV_DEFAULT", max_val=50.0, nans=(beta == 0.0), knobs={"mv_long_T": 1024, "mv6": 0}, x_special=first)
+        assert h.query("mv_long_rows") == 4, h.query("mv_long_rows")
+        h = pc.check_spmv_mv(be, A0, nvec, "N", alpha, beta, xo, yo, algo="SPMV_DEFAULT", max_val=50.0, nans=(beta == 0.0), knobs={"mv6": 0}, x_special=first)
+        assert h.query("mv_long_rows") == 5, h.query("mv_long_rows")
         h = pc.check_spmv_mv(be, A0, nvec, "N", alpha, beta, xo, yo, algo="SPMV_DEFAULT", max_val=50.0, nans=(beta == 0.0), knobs={"mv6": 0})
         assert h.query("mv_long_rows") == 5, h.query("mv_long_rows")            # automatic threshold: 4 x the average row, at least 64
     h = pc.check_spmv_mv(be, pc.randomized(oracle.random_crs(2000, 2000, 9, variance=3, seed=5)), 16, "N", 1.0, 0.0, "C", "C", algo="SPMV_DEFAULT")
@@ -626,3 +632,12 @@ def test_strided_rank1_vectors(be):
 
 def test_unsupported_type_pair_whatever_alpha(be):
     pc.check_unsupported_pair_leaves_y(be)
+
+
+@pytest.mark.parametrize("kind", ["rank1", "rank2", "struct"])
+@pytest.mark.parametrize("how", ["signed", "special"])
+def test_spmv_values_on_every_route(be, how, kind):
+    # values bit for bit against the sums of the expanded products (parity_cases.check_spmv_exact), one small structure per route, the route
+    # proved by plan queries: signed values; Inf / NaN / stored zeros in x and in A.values, finite values written back under the live handle
+    # (the GPU suite, test_gpu_spmv_values.py, runs the whole table in four modes with both offset types)
+    pc.check_spmv_values(be, how, kind, light=True)
