@@ -600,6 +600,14 @@ __device__ __forceinline__ void load_tile_codes(const uint16_t* __restrict__ wti
   }
 }
 
+// An empty statement that "uses" a loaded register: placed after the last load of a stream, it keeps the compiler from moving the
+// register's first real use (and with it the wait) up between the loads.  No code of its own; nothing to do under the emulator.
+#ifdef KK_EMU
+#define KK_USE_AFTER_ISSUE(v)
+#else
+#define KK_USE_AFTER_ISSUE(v) asm volatile("" : "+v"(v))
+#endif
+
 template <class AT, int STEPS, bool FULL>
 __device__ __forceinline__ void load_tile_win(const AT* __restrict__ values, const uint16_t* __restrict__ wtile,
                                               const int32_t* __restrict__ wmeta, int64_t b, int64_t ts, int64_t te, int t,
@@ -609,6 +617,8 @@ __device__ __forceinline__ void load_tile_win(const AT* __restrict__ values, con
   load_tile_codes<STEPS>(wtile, t, w);
   const int meta = wmeta[b * kWinMeta + (t & (kWinMeta - 1))];
   load_tile_values<AT, STEPS, FULL>(values, ts, te, t, v0, v1);
+  KK_UNROLL
+  for (int k = 0; k < STEPS; ++k) KK_USE_AFTER_ISSUE(w[k]);    // the codes are decoded after the last value load is out, not between them
   KK_UNROLL
   for (int k = 0; k < STEPS; ++k) {
     const int64_t idx = ts + (int64_t)k * SPAN + t * 2;
@@ -623,39 +633,51 @@ __device__ __forceinline__ void load_tile_win(const AT* __restrict__ values, con
   }
 }
 
-// Staged-x tile: values, codes, meta and the x chunks are all requested before anything is waited for; the x chunks go to
-// LDS (aliasing the product array), every work-item then picks its x entries out of LDS and the products replace them.
-template <class AT, class YT, int STEPS, bool FULL, bool NT, bool PAT>
-__device__ __forceinline__ void stage_products_win(const AT* __restrict__ values, const uint16_t* __restrict__ wtile,
-                                                   const int32_t* __restrict__ wmeta, const YT* __restrict__ x, int64_t ncols,
-                                                   YT* prod, int64_t b, int64_t ts, int64_t te, int t,
-                                                   const int32_t* __restrict__ pmeta) {
-  // PAT (workgroup-uniform template choice made by the caller from the tile's mode): the tile has a row-pattern record
+// Staged-x tile, in two steps so that the caller can put the tile's other requests (row bounds, old y) between them.
+// win_issue: everything that depends on the tile index alone -- window meta, pattern record, values, codes -- is requested, every load
+// unconditional (lanes past the record re-read its last word), nothing is looked at.
+template <class AT, int STEPS> struct WinTile { AT v0[STEPS], v1[STEPS]; unsigned w[STEPS]; int meta, prec0; };
+
+template <class AT, int STEPS, bool FULL, bool NT, bool PAT>
+__device__ __forceinline__ void win_issue(const AT* __restrict__ values, const uint16_t* __restrict__ wtile,
+                                          const int32_t* __restrict__ wmeta, const int32_t* __restrict__ pmeta, int64_t b,
+                                          int64_t ts, int64_t te, int t, WinTile<AT, STEPS>& W) {
+  W.meta  = wmeta[b * kWinMeta + (t & 63)];
+  W.prec0 = 0;                                                 // kPatW <= kBlock
+  if (PAT) W.prec0 = pmeta[b * kPatW + (t < kPatW ? t : kPatW - 1)];
+  load_tile_values<AT, STEPS, FULL, NT>(values, ts, te, t, W.v0, W.v1);
+  if (!PAT) load_tile_codes<STEPS, NT>(wtile, t, W.w);
+}
+
+// win_stage: waits for the meta alone, requests the x chunks (all of them: an unused chunk loads from a clamped legal address and is
+// not written), puts them into LDS (aliasing the product array); every work-item then picks its x entries out of LDS and the products
+// replace them.
+template <class AT, class YT, int STEPS, bool PAT>
+__device__ __forceinline__ void win_stage(WinTile<AT, STEPS>& W, const YT* __restrict__ x, int64_t ncols, YT* prod, int64_t b, int t,
+                                          const int32_t* __restrict__ pmeta) {
+  // PAT (workgroup-uniform template choice made by the caller from the tile's mode): the tile has a row-pattern record and no codes
   constexpr int SPAN = kBlock * 2, NPT = 2 * STEPS, TILE = kBlock * NPT;
   constexpr int CAPC = (TILE < kWinChunks * 64 ? TILE : kWinChunks * 64) / 64;     // chunks the LDS window can hold
   constexpr int CPW  = (CAPC + kBlock / 64 - 1) / (kBlock / 64);                     // chunks per wave
-  AT v0[STEPS], v1[STEPS];
-  unsigned w[STEPS];
+  constexpr int GRP  = STEPS < 4 ? STEPS : 4;                  // k-steps per batch of the x pick: 2 GRP table reads, then 2 GRP x reads in flight
+  const AT (&v0)[STEPS] = W.v0;
+  const AT (&v1)[STEPS] = W.v1;
+  const unsigned (&w)[STEPS] = W.w;
   const int lane = t & 63, wave = t >> 6;
-  const int meta = wmeta[b * kWinMeta + lane];
-  // PAT: a tile with a row-pattern record needs no per-nonzero codes at all
+  const int meta = W.meta;
   const int32_t* pm = PAT ? pmeta + b * kPatW : nullptr;
   const int nseg    = PAT ? pm[0] : 0;                         // workgroup-uniform, >= 1
-  int prec0 = 0;                                               // kPatW <= kBlock
-  if (PAT && t < kPatW) prec0 = pm[t];
-  load_tile_values<AT, STEPS, FULL, NT>(values, ts, te, t, v0, v1);
   YT xv[CPW];
   bool used[CPW];                                              // unused chunks are not written: the pattern record may sit there
   KK_UNROLL
   for (int i = 0; i < CPW; ++i) {
     const int c   = wave + i * (kBlock / 64);
     const int col = c < CAPC ? __shfl(meta, 2 * kWinCount + c, 64) : -1;            // wave-uniform
-    int64_t xi    = (int64_t)col + lane;
-    xi            = xi < ncols ? xi : ncols - 1;
     used[i]       = col >= 0;
-    xv[i]         = used[i] ? x[xi] : YT(0);
+    int64_t xi    = (int64_t)(used[i] ? col : 0) + lane;
+    xi            = xi < ncols ? xi : ncols - 1;
+    xv[i]         = x[xi];
   }
-  if (!PAT) load_tile_codes<STEPS, NT>(wtile, t, w);
   KK_UNROLL
   for (int i = 0; i < CPW; ++i) {
     const int c = wave + i * (kBlock / 64);
@@ -663,13 +685,16 @@ __device__ __forceinline__ void stage_products_win(const AT* __restrict__ values
   }
   int* sseg = reinterpret_cast<int*>(prod + TILE) - kPatW;     // the record sits behind the x window (the analysis leaves room)
   const short* stab = reinterpret_cast<const short*>(sseg + kPatTab);   // 16-bit (signed) slot tables
-  if (PAT && t < kPatW) sseg[t] = prec0;
+  if (PAT && t < kPatW) sseg[t] = W.prec0;
   __syncthreads();
   YT x0[STEPS], x1[STEPS];
   if (PAT) {
     // nonzero li -> (segment g, row, k): row = floor((li - first row start) / L) by a float reciprocal (exact: (j + 0.5) / L
     // stays 1/64 away from every integer), k by a full-rate 24-bit multiply; slot = T_g[k] + row.  One-segment tiles (no grid
-    // line boundary inside) need no search and keep the segment's constants in scalar registers.
+    // line boundary inside) need no search and keep the segment's constants in scalar registers.  Tiles of up to four segments
+    // (one grid line end inside) keep all four segments' constants in scalar registers too and select per nonzero by compares;
+    // only tiles of five to eight segments read the constants of a nonzero's segment from the record in LDS.  Every branch
+    // works in batches of 2 GRP nonzeros: all their table reads, then all their x reads -- no LDS round trip per nonzero.
     if (nseg == 1) {
       const int jadd = pm[kPatRec + 1];
       const unsigned L = (unsigned)pm[kPatRec + 2];
@@ -684,21 +709,60 @@ __device__ __forceinline__ void stage_products_win(const AT* __restrict__ values
           if (h == 0) x0[k] = prod[slot]; else x1[k] = prod[slot];
         }
       }
+    } else if (nseg <= 4) {
+      const int sb1 = pm[1], sb2 = pm[2], sb3 = pm[3];         // INT_MAX where the tile has fewer segments
+      const int ja0 = pm[kPatRec + 1], ja1 = pm[kPatRec + 5], ja2 = pm[kPatRec + 9], ja3 = pm[kPatRec + 13];
+      const int sl0 = pm[kPatRec + 2], sl1 = pm[kPatRec + 6], sl2 = pm[kPatRec + 10], sl3 = pm[kPatRec + 14];
+      const int sm0 = pm[kPatRec + 3], sm1 = pm[kPatRec + 7], sm2 = pm[kPatRec + 11], sm3 = pm[kPatRec + 15];
+      KK_UNROLL
+      for (int k0 = 0; k0 < STEPS; k0 += GRP) {
+        int ti[2 * GRP], rw[2 * GRP], sl[2 * GRP];
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) {
+          const int li  = (k0 + q / 2) * SPAN + t * 2 + (q & 1);
+          const bool c1 = li >= sb1, c2 = li >= sb2, c3 = li >= sb3;
+          const int ja  = c3 ? ja3 : c2 ? ja2 : c1 ? ja1 : ja0;
+          const int sl_ = c3 ? sl3 : c2 ? sl2 : c1 ? sl1 : sl0;
+          const int sm  = c3 ? sm3 : c2 ? sm2 : c1 ? sm1 : sm0;
+          const int tb  = c3 ? 3 * kPatLen : c2 ? 2 * kPatLen : c1 ? kPatLen : 0;
+          const unsigned j   = (unsigned)(li + ja);
+          const unsigned row = (unsigned)(((float)j + 0.5f) * __int_as_float(sm));
+          ti[q] = tb + (int)(j - KK_UMUL24(row, (unsigned)sl_));
+          rw[q] = (int)row;
+        }
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) sl[q] = (int)stab[ti[q]] + rw[q];
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) {
+          if ((q & 1) == 0) x0[k0 + q / 2] = prod[sl[q]]; else x1[k0 + q / 2] = prod[sl[q]];
+        }
+      }
     } else {
       const int sb1 = pm[1], sb2 = pm[2], sb3 = pm[3], sb4 = pm[4], sb5 = pm[5], sb6 = pm[6], sb7 = pm[7];
       KK_UNROLL
-      for (int k = 0; k < STEPS; ++k) {
+      for (int k0 = 0; k0 < STEPS; k0 += GRP) {
+        int ti[2 * GRP], rw[2 * GRP], sl[2 * GRP], ja[2 * GRP], sl_[2 * GRP], sm[2 * GRP];
         KK_UNROLL
-        for (int h = 0; h < 2; ++h) {
-          const int li = k * SPAN + t * 2 + h;
-          int g = (li >= sb1) + (li >= sb2) + (li >= sb3);
-          if (nseg > 4) g += (li >= sb4) + (li >= sb5) + (li >= sb6) + (li >= sb7);      // workgroup-uniform
-          const int* rec     = sseg + kPatRec + 4 * g;
-          const unsigned j   = (unsigned)(li + rec[1]);
-          const unsigned L   = (unsigned)rec[2];
-          const unsigned row = (unsigned)(((float)j + 0.5f) * __int_as_float(rec[3]));
-          const int slot     = (int)stab[g * kPatLen + (int)(j - KK_UMUL24(row, L))] + (int)row;
-          if (h == 0) x0[k] = prod[slot]; else x1[k] = prod[slot];
+        for (int q = 0; q < 2 * GRP; ++q) {
+          const int li   = (k0 + q / 2) * SPAN + t * 2 + (q & 1);
+          const int g    = (li >= sb1) + (li >= sb2) + (li >= sb3) + (li >= sb4) + (li >= sb5) + (li >= sb6) + (li >= sb7);
+          const int* rec = sseg + kPatRec + 4 * g;
+          ja[q] = rec[1]; sl_[q] = rec[2]; sm[q] = rec[3];
+          ti[q] = g * kPatLen;
+        }
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) {
+          const int li       = (k0 + q / 2) * SPAN + t * 2 + (q & 1);
+          const unsigned j   = (unsigned)(li + ja[q]);
+          const unsigned row = (unsigned)(((float)j + 0.5f) * __int_as_float(sm[q]));
+          ti[q] += (int)(j - KK_UMUL24(row, (unsigned)sl_[q]));
+          rw[q]  = (int)row;
+        }
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) sl[q] = (int)stab[ti[q]] + rw[q];
+        KK_UNROLL
+        for (int q = 0; q < 2 * GRP; ++q) {
+          if ((q & 1) == 0) x0[k0 + q / 2] = prod[sl[q]]; else x1[k0 + q / 2] = prod[sl[q]];
         }
       }
     }
@@ -803,12 +867,19 @@ template <class YT> __device__ __forceinline__ YT strided_lds_sum(const YT* prod
 }
 
 // The planned kernel (nnz-split tiles).  What bounds a kernel that needs ~100 KB in flight per CU is the DEPENDENCY CHAIN
-// each tile goes through: the tile descriptor (first row + "starts inside a row" flag: one scalar load) is requested first,
-// the streaming loads do not depend on it, and the per-lane row bounds row_map[r], row_map[r+1] are requested together
-// with the x gathers -- so a tile sees two memory latencies (stream, then gather + bounds).  After the barrier the row
-// reduction touches only LDS and registers.
+// each tile goes through, so the order of issue is: (1) the tile descriptor (first row + "starts inside a row" flag: one scalar
+// load); (2) what depends on the tile index alone -- window meta, pattern record, then the value stream (with codes / entries
+// where the mode has them); (3) the per-lane row bounds row_map[r], row_map[r+1] and, for beta != 0, the old y, which need the
+// descriptor but nothing from memory; (4) a counted wait for the meta alone, then the x chunks (staged modes), or for the columns,
+// then the x gathers (plain / code tiles).  No vector-memory wait comes before the whole stream is in flight, and a staged tile
+// sees one scalar and two vector-memory latencies (stream, then x chunks).  That holds only while every load of (2) and (3) is
+// UNCONDITIONAL and its result is not touched before its real use: the row bounds are loaded with the row clamped into the
+// tile's legal range, kept as the raw loaded words, and validity, widening and the clamps to the tile are applied after the
+// barrier, where i0 / i1 are formed (a load inside `if (valid)` followed by a widening makes the compiler drain vmcnt at the
+// join -- one loaded HBM latency per tile with nothing in flight).  After the barrier the row reduction touches only LDS and
+// registers; tiles with more virtual rows than row groups load the bounds of their later passes inside the loop.
 // The column analysis is PER TILE (tinfo[b]): kTilePlain reads entries and gathers x with quad-dealt loads, kTileCodes takes
-// its columns from the plan's 16-bit window codes, kTileStaged also stages the tile's x ranges in LDS (stage_products_win),
+// its columns from the plan's 16-bit window codes, kTileStaged also stages the tile's x ranges in LDS (win_issue / win_stage),
 // kTilePattern decodes a row-pattern record and reads no per-nonzero code at all.  One tile the codes cannot cover costs
 // that tile its codes, not the matrix.  Each mode is its own instantiation (MODE) launched over the plan's LIST of the
 // tiles of that mode (null = every tile): one kernel with all four paths needs 135-152 registers per work-item where the
@@ -845,8 +916,12 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
 
   AT v0[STEPS], v1[STEPS];
   int c0[STEPS], c1[STEPS];
-  if (MODE >= kTileStaged) {
-    // nothing to load here: stage_products_win requests values, codes and x chunks together
+  WinTile<AT, STEPS> W;
+  if (MODE == kTilePattern) {                                   // records exist for full tiles only (the ragged last tile keeps its codes)
+    win_issue<AT, STEPS, true, NT, true>(values, wtile, wmeta, pmeta, b, s, e, t, W);
+  } else if (MODE == kTileStaged) {
+    if (full) win_issue<AT, STEPS, true, NT, false>(values, wtile, wmeta, pmeta, b, s, e, t, W);
+    else      win_issue<AT, STEPS, false, NT, false>(values, wtile, wmeta, pmeta, b, s, e, t, W);
   } else if (MODE == kTileCodes) {
     if (full) load_tile_win<AT, STEPS, true>(values, wtile, wmeta, b, s, e, t, v0, v1, c0, c1);
     else      load_tile_win<AT, STEPS, false>(values, wtile, wmeta, b, s, e, t, v0, v1, c0, c1);
@@ -862,29 +937,31 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
   int G = 1;
   while (G < kWave && nv * (G * 2) <= kBlock) G *= 2;
   const int lane = t & (G - 1), grp = t / G, ngrp = kBlock / G;
-  // virtual row j -> matrix row r = ra + j - has_head (r = ra-1 is the head's row); bounds for the first pass
+  // virtual row j -> matrix row r = ra + j - has_head (r = ra-1 is the head's row); bounds for the first pass: requested by EVERY
+  // lane (lanes without a row: from a row of the tile, 0 <= rc < rb <= nrows) and left as loaded until the stream is staged
   bool valid = grp < nv;
   int64_t r  = ra + grp - has_head;
-  int64_t rs = 0, re = 0;
-  if (valid) {
-    if (KK_ABL(16)) { rs = s + (int64_t)grp * 27; re = rs + 27; }
-    else { rs = (int64_t)row_map[r]; re = (int64_t)row_map[r + 1]; }
-  }
+  int64_t rc = r > 0 ? r : 0;
+  rc         = rc < rb ? rc : rb - 1;                  // rb >= 1: row 0 starts before the end of any tile
+  OffT rs_raw = OffT(0), re_raw = OffT(0);
+  if (!KK_ABL(16)) { rs_raw = row_map[rc]; re_raw = row_map[rc + 1]; }
   // beta != 0: the old y of the first pass' rows is requested now, with everything else, instead of right before the store
   YT yold = YT(0);
-  if (beta != YT(0) && valid && lane == 0 && r >= 0) yold = y[r];
+  if (beta != YT(0)) yold = y[rc];
 
-  if (MODE == kTilePattern) {                                   // records exist for full tiles only (the ragged last tile keeps its codes)
-    stage_products_win<AT, YT, STEPS, true, NT, true>(values, wtile, wmeta, x, ncols, prod, b, s, e, t, pmeta);
-  } else if (MODE == kTileStaged) {
-    if (full) stage_products_win<AT, YT, STEPS, true, NT, false>(values, wtile, wmeta, x, ncols, prod, b, s, e, t, nullptr);
-    else      stage_products_win<AT, YT, STEPS, false, NT, false>(values, wtile, wmeta, x, ncols, prod, b, s, e, t, nullptr);
+  if (MODE >= kTileStaged) {
+    win_stage<AT, YT, STEPS, MODE == kTilePattern>(W, x, ncols, prod, b, t, pmeta);
   } else {
     if (full) stage_products<AT, YT, STEPS, true, true>(x, prod, t, v0, v1, c0, c1);
     else      stage_products<AT, YT, STEPS, false, false>(x, prod, t, v0, v1, c0, c1);
   }
   if (!KK_ABL(32)) __syncthreads();
 
+  int64_t rs = 0, re = 0;
+  if (valid) {
+    if (KK_ABL(16)) { rs = s + (int64_t)grp * 27; re = rs + 27; }
+    else { rs = (int64_t)rs_raw; re = (int64_t)re_raw; }
+  }
   for (int64_t base = 0; base < nv; base += ngrp) {
     if (base > 0) {
       valid = (base + grp) < nv;
