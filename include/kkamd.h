@@ -1,5 +1,5 @@
 /* kkamd.h -- C ABI of libkkamd.so: the MI355X (gfx950) native implementation of the
- * KokkosSparse::spmv / KokkosSparse::spgemm hot path.
+ * KokkosSparse::spmv / KokkosSparse::spgemm / KokkosSparse::sptrsv hot path.
  *
  * This is the drop-in boundary.  It sits exactly where kokkos-kernels plugs vendor libraries in
  * today -- the "TPL specialisation" layer -- and takes what those specialisations hand over:
@@ -394,6 +394,59 @@ int kkamd_dist_spgemm_numeric(kkamd_dist_spgemm_t* op, int64_t m_local, int64_t 
                               kkamd_stream_t stream);
 int kkamd_dist_spgemm_query(const kkamd_dist_spgemm_t* op, const char* key, int64_t* value);
 
+
+/* ------------------------------------------------------------------------------------------------
+ * Sparse triangular solve.  Replaces KokkosSparse::sptrsv_symbolic / sptrsv_solve for a CrsMatrix triangle
+ * (sparse/src/KokkosSparse_sptrsv.hpp:54-122,268-411; native level scheduling sparse/impl/KokkosSparse_sptrsv_symbolic_impl.hpp:156-214
+ * and :569-640, solve semantics sparse/impl/KokkosSparse_sptrsv_solve_impl.hpp:434-566; the reference's only vendor plug-in is cuSPARSE,
+ * sparse/tpls/KokkosSparse_sptrsv_*_tpl_spec_*.hpp).  Solves L x = b or U x = b for a square CRS triangle whose diagonal is stored:
+ * x[i] = (b[i] - sum_{j != i} a_ij x[j]) / a_ii.  Entries of a row may come in any order, repeated off-diagonal columns are summed, b may
+ * be x, the old content of x is never read.  b and x are rank 1 and contiguous (the reference static-asserts rank 1, :291-292); type pairs
+ * (F64,F64) and (F32,F32).
+ *
+ * The handle is the analogue of SPTRSVHandle (sparse/src/KokkosSparse_sptrsv_handle.hpp): it keeps the level sets -- level_list,
+ * nodes_per_level, nodes_grouped_by_level, defined exactly as in the reference: level(i) = 1 + max level(col) over the row's off-diagonal
+ * columns, 1 for a row without any; rows ascending inside a level -- and every row's diagonal position, never values.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_sptrsv_handle kkamd_sptrsv_handle_t;
+/* KokkosSparse::Experimental::SPTRSVAlgorithm (sparse/src/KokkosSparse_sptrsv_handle.hpp:42-47).  The three level-scheduled values run
+ * the same kernels, one launch per level: RP with one lane per row and no chaining, TP1 with the lanes per row chosen per level (the smallest power of two
+ * that covers the level's mean row length), TP1CHAIN the same plus runs of narrow levels chained into single-workgroup launches (the reference's TP1CHAIN
+ * idea).  SPTRSV_CUSPARSE returns KKAMD_ERR_UNSUPPORTED at create. */
+typedef enum {
+  KKAMD_SPTRSV_SEQLVLSCHD_RP       = 0,
+  KKAMD_SPTRSV_SEQLVLSCHD_TP1      = 1,
+  KKAMD_SPTRSV_SEQLVLSCHD_TP1CHAIN = 2,
+  KKAMD_SPTRSV_CUSPARSE            = 3
+} kkamd_sptrsv_algorithm;
+/* KokkosKernelsHandle::create_sptrsv_handle(algm, nrows, lower_tri) / destroy_sptrsv_handle (sparse/src/KokkosKernels_Handle.hpp:777-797) */
+int kkamd_sptrsv_create(kkamd_sptrsv_handle_t** handle, int algorithm, int64_t num_rows, int lower_tri);
+int kkamd_sptrsv_destroy(kkamd_sptrsv_handle_t* handle);
+/* sptrsv_symbolic(handle, rowmap, entries) (sparse/src/KokkosSparse_sptrsv.hpp:54-122).  Validates first, in one pass that indexes nothing
+ * by a column it has not yet checked -- KKAMD_ERR_INVALID_ARG, the first offending row named in kkamd_last_error(), when num_rows differs
+ * from the handle's, a column is outside [0, num_rows), an entry is on the wrong side of the diagonal, or a row has no or more than one
+ * diagonal entry --, then builds the level sets on the device (no host pass over the entries; one stream synchronisation per level).  May be
+ * repeated on one handle (analyses again).  Synchronises the stream, because it returns counts. */
+int kkamd_sptrsv_symbolic(kkamd_sptrsv_handle_t* handle, int64_t num_rows, const void* d_row_map, const int32_t* d_entries, int offset_type,
+                          kkamd_stream_t stream);
+/* sptrsv_solve(handle, rowmap, entries, values, b, x) (sparse/src/KokkosSparse_sptrsv.hpp:268-411).  KKAMD_ERR_STATE before a completed
+ * symbolic call, KKAMD_ERR_UNSUPPORTED for another value type; otherwise asynchronous on the stream: allocates nothing, synchronises
+ * nothing, reads the caller's arrays at every call (the structure must be the one analysed). */
+int kkamd_sptrsv_solve(kkamd_sptrsv_handle_t* handle, int64_t num_rows, const void* d_row_map, const int32_t* d_entries, const void* d_values,
+                       const void* d_b, void* d_x, int offset_type, int value_type, kkamd_stream_t stream);
+/* Knobs (values outside the ranges: KKAMD_ERR_INVALID_ARG; the analogue of SPTRSVHandle::set_team_size / set_vector_size /
+ * set_chain_threshold, sptrsv_handle.hpp:749-760,860-870):
+ *   "lanes_per_row"  0 (default) = by level, or 1, 2, 4, ..., 64; ignored by SEQLVLSCHD_RP
+ *   "chain_rows"     a level with at most this many rows may join a chain (SEQLVLSCHD_TP1CHAIN only); 0 = never; default 64 (measured:
+ *                    DESIGN.md 4.5; the reference defaults its threshold to the team size)
+ *   "chain_levels"   the most levels one chain launch covers (>= 1, default 1024): bounds how long a single launch runs */
+int kkamd_sptrsv_set(kkamd_sptrsv_handle_t* handle, const char* key, int value);
+/* "num_levels", "symbolic_complete", "lower_tri", "algorithm", "num_rows", "max_level_rows", "launches" (kernel launches of one solve),
+ * "chain_launches", "chained_levels", "plan_bytes" (HBM the handle keeps), and the three knobs */
+int kkamd_sptrsv_get(const kkamd_sptrsv_handle_t* handle, const char* key, int64_t* value);
+/* to a HOST buffer of `count` int32: "level_list" (num_rows entries, 1-based levels as in the reference), "nodes_per_level" (num_levels),
+ * "nodes_grouped_by_level" (num_rows) */
+int kkamd_sptrsv_export(const kkamd_sptrsv_handle_t* handle, const char* what, void* h_out, int64_t count);
 
 /* ------------------------------------------------------------------------------------------------
  * Helpers either side of the path (KokkosSparse::sort_crs_matrix, sparse/src/KokkosSparse_SortCrs.hpp:43-120;

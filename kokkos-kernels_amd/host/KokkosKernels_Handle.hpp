@@ -1,6 +1,6 @@
-// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM path uses
-// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482): create / get / destroy of the SpGEMM
-// sub-handle plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
+// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM and SPTRSV paths use
+// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862): create / get / destroy of the SpGEMM
+// and SPTRSV sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
 // decision, like KOKKOSKERNELS_VERBOSE).  The team / vector / shared-memory / scheduling setters are HINTS in the reference
 // too -- its rocSPARSE and cuSPARSE paths take and ignore them, and its driver and unit tests set them before every spgemm
 // (perf_test/sparse/KokkosSparse_spgemm.cpp:311-317, sparse/unit_test/Test_Sparse_spgemm.hpp:91-92) -- so they are accepted,
@@ -8,6 +8,7 @@
 // under verbose) and have no effect: launch shapes and LDS tables follow the row bins.
 #pragma once
 #include "KokkosSparse_spgemm_handle.hpp"
+#include "KokkosSparse_sptrsv_handle.hpp"
 
 namespace KokkosKernels { namespace Experimental {
 
@@ -22,10 +23,14 @@ class KokkosKernelsHandle {
   using const_nnz_lno_t  = const nnz_lno_t;
   using const_nnz_scalar_t = const nnz_scalar_t;
   using HandleExecSpace  = ExecutionSpace;
+  using HandleTempMemorySpace       = TemporaryMemorySpace;
+  using HandlePersistentMemorySpace = PersistentMemorySpace;
   using SPGEMMHandleType = KokkosSparse::SPGEMMHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace,
                                                      TemporaryMemorySpace, PersistentMemorySpace>;
+  using SPTRSVHandleType = KokkosSparse::Experimental::SPTRSVHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace,
+                                                                   TemporaryMemorySpace, PersistentMemorySpace>;
   KokkosKernelsHandle() = default;
-  ~KokkosKernelsHandle() { destroy_spgemm_handle(); }
+  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); }
   KokkosKernelsHandle(const KokkosKernelsHandle&)            = delete;
   KokkosKernelsHandle& operator=(const KokkosKernelsHandle&) = delete;
 
@@ -42,6 +47,17 @@ class KokkosKernelsHandle {
   }
   SPGEMMHandleType* get_spgemm_handle() { return spgemm_; }
   void destroy_spgemm_handle() { delete spgemm_; spgemm_ = nullptr; }
+
+  // SPTRSV sub-handle (:765-783,848-862); the hints given to this handle go to it as in the reference (:773-774)
+  SPTRSVHandleType* get_sptrsv_handle() { return sptrsv_; }
+  void create_sptrsv_handle(KokkosSparse::Experimental::SPTRSVAlgorithm algm, size_type nrows, bool lower_tri, size_type block_size = 0) {
+    destroy_sptrsv_handle();
+    sptrsv_ = new SPTRSVHandleType(algm, nrows, lower_tri, block_size);
+    sptrsv_->set_team_size(team_work_size);
+    sptrsv_->set_vector_size(vector_size);
+  }
+  void destroy_sptrsv_handle() { delete sptrsv_; sptrsv_ = nullptr; }
+  bool is_sptrsv_lower_tri() { return sptrsv_->is_lower_tri(); }
 
   // hints of the reference (:380-465; defaults :203-215): remembered, forwarded, without effect on gfx950
   void set_team_work_size(const int v) { team_work_size = v; hint("team_work_size", v); }
@@ -67,6 +83,7 @@ class KokkosKernelsHandle {
   int vector_size           = -1;
   bool use_dynamic_scheduling = true;
   SPGEMMHandleType* spgemm_ = nullptr;
+  SPTRSVHandleType* sptrsv_ = nullptr;
   bool verbose_             = false;
 };
 

@@ -321,6 +321,7 @@ class KokkosKernelsHandle:
     def __init__(self, backend=None):
         self.backend = backend
         self._spgemm = None
+        self._sptrsv = None
 
     def create_spgemm_handle(self, algo="SPGEMM_KK"):
         """algo: a KokkosSparse::SPGEMMAlgorithm name (sparse/src/KokkosSparse_spgemm_handle.hpp:44-93).  SPGEMM_DEBUG / SPGEMM_SERIAL
@@ -338,6 +339,108 @@ class KokkosKernelsHandle:
         if self._spgemm is not None:
             self._spgemm.destroy()
         self._spgemm = None
+
+    def create_sptrsv_handle(self, algo, nrows, lower_tri):
+        """create_sptrsv_handle(algm, nrows, lower_tri) (sparse/src/KokkosKernels_Handle.hpp:777-786); algo: a
+        KokkosSparse::Experimental::SPTRSVAlgorithm name (sparse/src/KokkosSparse_sptrsv_handle.hpp:42-47)"""
+        self.backend = self.backend or torch_backend()
+        if algo not in _SPTRSV_ALGOS:
+            raise RuntimeError("Invalid SPTRSVAlgorithm name")
+        self.destroy_sptrsv_handle()
+        self._sptrsv = _SptrsvHandle(self.backend, algo, nrows, lower_tri)
+
+    def get_sptrsv_handle(self): return self._sptrsv
+
+    def destroy_sptrsv_handle(self):
+        if self._sptrsv is not None:
+            self._sptrsv.destroy()
+        self._sptrsv = None
+
+
+_SPTRSV_ALGOS = {"SEQLVLSCHD_RP": 0, "SEQLVLSCHD_TP1": 1, "SEQLVLSCHD_TP1CHAIN": 2, "SPTRSV_CUSPARSE": 3}
+
+
+class _SptrsvHandle:
+    """KokkosSparse::Experimental::SPTRSVHandle as far as the level-scheduled solve uses it (sparse/src/KokkosSparse_sptrsv_handle.hpp):
+    algorithm, size and triangle, the level sets of the symbolic phase, and this library's knobs."""
+
+    def __init__(self, backend, algo, nrows, lower_tri):
+        self.backend, self.algo = backend, algo
+        self.h = C.c_void_p()
+        check(backend.lib, backend.lib.kkamd_sptrsv_create(C.byref(self.h), _SPTRSV_ALGOS[algo], int(nrows), 1 if lower_tri else 0))
+
+    def set(self, key, value):
+        """"lanes_per_row", "chain_rows", "chain_levels" (kkamd_sptrsv_set)"""
+        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_set(self.h, key.encode(), int(value)))
+
+    def get(self, key):
+        v = C.c_int64()
+        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_get(self.h, key.encode(), C.byref(v)))
+        return int(v.value)
+
+    def export(self, what):
+        """"level_list", "nodes_per_level" or "nodes_grouped_by_level" as a host int32 array"""
+        n = self.get("num_levels") if what == "nodes_per_level" else self.get("num_rows")
+        out = np.zeros(n, dtype=np.int32)
+        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_export(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def get_algorithm(self): return self.algo
+    def get_nrows(self): return self.get("num_rows")
+    def is_lower_tri(self): return bool(self.get("lower_tri"))
+    def is_upper_tri(self): return not self.is_lower_tri()
+    def get_num_levels(self): return self.get("num_levels")
+    def is_symbolic_complete(self): return bool(self.get("symbolic_complete"))
+
+    def destroy(self):
+        if self.h:
+            self.backend.lib.kkamd_sptrsv_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _sptrsv_handle(kh, who):
+    th = kh.get_sptrsv_handle() if kh is not None else None
+    if th is None:
+        raise ValueError("KokkosSparse::%s: the given KernelHandle does not have an SPTRSV handle associated with it." % who)
+    return th
+
+
+def sptrsv_symbolic(kh, row_map, entries):
+    """KokkosSparse::sptrsv_symbolic(handle, rowmap, entries) (sparse/src/KokkosSparse_sptrsv.hpp:54-122): validates the triangle and
+    builds the level sets on the device.  May be repeated."""
+    th = _sptrsv_handle(kh, "sptrsv_symbolic")
+    be, lib = th.backend, th.backend.lib
+    check(lib, lib.kkamd_sptrsv_symbolic(th.h, int(row_map.shape[0]) - 1, be.ptr(row_map), be.ptr(entries), _offset_type(row_map), be.stream()))
+
+
+def sptrsv_solve(kh, row_map, entries, values, b, x):
+    """KokkosSparse::sptrsv_solve(handle, rowmap, entries, values, b, x) (sparse/src/KokkosSparse_sptrsv.hpp:268-411): x := A^-1 b on the
+    backend's current stream; b may be x.  b and x are rank 1 and contiguous."""
+    th = _sptrsv_handle(kh, "sptrsv_solve")
+    be, lib = th.backend, th.backend.lib
+    if len(b.shape) != 1 or len(x.shape) != 1:
+        raise RuntimeError("KokkosSparse::sptrsv_solve: b and x must have rank 1")
+    n = int(row_map.shape[0]) - 1
+    if b.shape[0] != n or x.shape[0] != n:
+        raise RuntimeError("KokkosSparse::sptrsv_solve: Dimensions do not match: A: %d x %d, b: %d, x: %d" % (n, n, b.shape[0], x.shape[0]))
+    if _vec_stride(b, "sptrsv_solve") != 1 or _vec_stride(x, "sptrsv_solve") != 1:
+        raise RuntimeError("KokkosSparse::sptrsv_solve: b and x must be contiguous")
+    if _np_dtype(values) != _np_dtype(x) or _np_dtype(b) != _np_dtype(x):
+        raise RuntimeError("KokkosSparse::sptrsv_solve: values, b and x must have one scalar type")
+    try:
+        check(lib, lib.kkamd_sptrsv_solve(th.h, n, be.ptr(row_map), be.ptr(entries), be.ptr(values), be.ptr(b), be.ptr(x),
+                                          _offset_type(row_map), _scalar_type(x), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))   # std::invalid_argument in the reference
+        raise
+    return x
 
 
 def spgemm_symbolic(kh, A, transposeA, B, transposeB, Cmat=None, allocate=True):
