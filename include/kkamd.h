@@ -229,7 +229,8 @@ int kkamd_set_default(const char* key, int value);
  * (sparse/src/KokkosSparse_spmv_handle.hpp:273-277), vendor analyses of this kind ask for the same call (rocsparse update-values). */
 int kkamd_spmv_plan_values_changed(kkamd_spmv_plan_t* plan);
 /* What the analysis of a plan produced: "tile" (nnz per workgroup, 0 = no tiling), "tiles", per-mode tile counts "plain_tiles" /
- * "code_tiles" / "staged_tiles" / "pattern_tiles", "window_codes" (1 if any tile uses the column analysis), "window_staged_x",
+ * "code_tiles" / "staged_tiles" / "pattern_tiles", "pattern_list_identity" (1 if the pattern tiles are tiles 0 ... pattern_tiles - 1, so
+ * that their launch reads no tile list), "window_codes" (1 if any tile uses the column analysis), "window_staged_x",
  * "plan_bytes" (HBM the analysis keeps), "transpose_cached", rank 2: "mv_tiles", "mv_staged_tiles", "mv_order" (order in use),
  * "mv_period" (far stride found), "mv_plan_bytes", plane-marching kernel: "mv4_workgroups" (0 = not in use), "mv4_other_rows"
  * (rows left to its gather kernel), "mv4_stencil" (entries of the stencil), "mv4_near_stride"; matrix-core kernel: "mv5_tiles" (described

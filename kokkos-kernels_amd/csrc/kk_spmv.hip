@@ -602,10 +602,14 @@ __device__ __forceinline__ void load_tile_codes(const uint16_t* __restrict__ wti
 
 // An empty statement that "uses" a loaded register: placed after the last load of a stream, it keeps the compiler from moving the
 // register's first real use (and with it the wait) up between the loads.  No code of its own; nothing to do under the emulator.
+// KK_USE_SCALAR_AFTER_ISSUE: the same for a wave-uniform word in a scalar register (a kernel argument) -- its scalar load stays in front of
+// the statement (the compiler would otherwise sink it to its first use, behind the stream and behind a scalar wait of its own).
 #ifdef KK_EMU
 #define KK_USE_AFTER_ISSUE(v)
+#define KK_USE_SCALAR_AFTER_ISSUE(v)
 #else
 #define KK_USE_AFTER_ISSUE(v) asm volatile("" : "+v"(v))
+#define KK_USE_SCALAR_AFTER_ISSUE(v) asm volatile("" : "+s"(v))
 #endif
 
 template <class AT, int STEPS, bool FULL>
@@ -634,31 +638,61 @@ __device__ __forceinline__ void load_tile_win(const AT* __restrict__ values, con
 }
 
 // Staged-x tile, in two steps so that the caller can put the tile's other requests (row bounds, old y) between them.
-// win_issue: everything that depends on the tile index alone -- window meta, pattern record, values, codes -- is requested, every load
-// unconditional (lanes past the record re-read its last word), nothing is looked at.
-template <class AT, int STEPS> struct WinTile { AT v0[STEPS], v1[STEPS]; unsigned w[STEPS]; int meta, prec0; };
+// win_issue: everything that depends on the tile index alone is requested, every load unconditional (lanes past the record re-read
+// its last word), nothing is looked at.  A pattern tile uses nothing of the window meta but the first columns of its x chunks
+// ([2 kWinCount, kWinMeta)); wave w stages the chunks w CPW ... w CPW + CPW - 1, so their columns are wave-uniform words next to each
+// other: one scalar load, no vector load of the meta, and the x chunks (all of them: an unused chunk loads from a clamped legal
+// address and is not written) are requested here, IN FRONT of the record and the value stream -- x is in LDS and the x pick under
+// way while the values arrive (measured against values first, profiles/LABBOOK_round8.md).  A staged tile without a record
+// requests its meta (vector: the code decode needs it per lane), values and codes; its x chunks follow in win_stage.
+template <int STEPS> struct WinGeom {
+  static constexpr int TILE = kBlock * 2 * STEPS;
+  static constexpr int CAPC = (TILE < kWinChunks * 64 ? TILE : kWinChunks * 64) / 64;   // chunks the LDS window can hold
+  static constexpr int CPW  = (CAPC + kBlock / 64 - 1) / (kBlock / 64);                 // chunks per wave
+};
+template <class AT, class YT, int STEPS> struct WinTile {
+  AT v0[STEPS], v1[STEPS];
+  unsigned w[STEPS];
+  int meta, prec0, ccol[WinGeom<STEPS>::CPW];
+  YT xv[WinGeom<STEPS>::CPW];
+};
 
-template <class AT, int STEPS, bool FULL, bool NT, bool PAT>
+template <class AT, class YT, int STEPS, bool FULL, bool NT, bool PAT>
 __device__ __forceinline__ void win_issue(const AT* __restrict__ values, const uint16_t* __restrict__ wtile,
-                                          const int32_t* __restrict__ wmeta, const int32_t* __restrict__ pmeta, int64_t b,
-                                          int64_t ts, int64_t te, int t, WinTile<AT, STEPS>& W) {
-  W.meta  = wmeta[b * kWinMeta + (t & 63)];
+                                          const int32_t* __restrict__ wmeta, const int32_t* __restrict__ pmeta,
+                                          const YT* __restrict__ x, int64_t ncols, int64_t b, int64_t ts, int64_t te, int t,
+                                          WinTile<AT, YT, STEPS>& W) {
+  constexpr int CPW = WinGeom<STEPS>::CPW;
+  W.meta  = 0;
   W.prec0 = 0;                                                 // kPatW <= kBlock
-  if (PAT) W.prec0 = pmeta[b * kPatW + (t < kPatW ? t : kPatW - 1)];
+  if (PAT) {
+    static_assert(!PAT || CPW * (kBlock / 64) == WinGeom<STEPS>::CAPC, "every wave stages CPW chunks of the window");
+    const int32_t* cm = wmeta + b * kWinMeta + 2 * kWinCount + KK_UNIFORM(t >> 6) * CPW;      // wave-uniform address
+    KK_UNROLL
+    for (int i = 0; i < CPW; ++i) W.ccol[i] = cm[i];
+    KK_UNROLL
+    for (int i = 0; i < CPW; ++i) {
+      int64_t xi = (int64_t)(W.ccol[i] >= 0 ? W.ccol[i] : 0) + (t & 63);
+      xi         = xi < ncols ? xi : ncols - 1;
+      W.xv[i]    = x[xi];
+    }
+    W.prec0 = pmeta[b * kPatW + (t < kPatW ? t : kPatW - 1)];
+  } else {
+    W.meta = wmeta[b * kWinMeta + (t & 63)];
+  }
   load_tile_values<AT, STEPS, FULL, NT>(values, ts, te, t, W.v0, W.v1);
   if (!PAT) load_tile_codes<STEPS, NT>(wtile, t, W.w);
 }
 
-// win_stage: waits for the meta alone, requests the x chunks (all of them: an unused chunk loads from a clamped legal address and is
-// not written), puts them into LDS (aliasing the product array); every work-item then picks its x entries out of LDS and the products
-// replace them.
+// win_stage: a staged tile without a record waits (counted) for its meta alone and requests its x chunks (all of them, as above); both
+// kinds put the chunks into LDS (aliasing the product array) -- a pattern tile with a counted wait that leaves record and values in
+// flight --; every work-item then picks its x entries out of LDS and the products replace them.
 template <class AT, class YT, int STEPS, bool PAT>
-__device__ __forceinline__ void win_stage(WinTile<AT, STEPS>& W, const YT* __restrict__ x, int64_t ncols, YT* prod, int64_t b, int t,
+__device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* __restrict__ x, int64_t ncols, YT* prod, int64_t b, int t,
                                           const int32_t* __restrict__ pmeta) {
   // PAT (workgroup-uniform template choice made by the caller from the tile's mode): the tile has a row-pattern record and no codes
   constexpr int SPAN = kBlock * 2, NPT = 2 * STEPS, TILE = kBlock * NPT;
-  constexpr int CAPC = (TILE < kWinChunks * 64 ? TILE : kWinChunks * 64) / 64;     // chunks the LDS window can hold
-  constexpr int CPW  = (CAPC + kBlock / 64 - 1) / (kBlock / 64);                     // chunks per wave
+  constexpr int CAPC = WinGeom<STEPS>::CAPC, CPW = WinGeom<STEPS>::CPW;
   constexpr int GRP  = STEPS < 4 ? STEPS : 4;                  // k-steps per batch of the x pick: 2 GRP table reads, then 2 GRP x reads in flight
   const AT (&v0)[STEPS] = W.v0;
   const AT (&v1)[STEPS] = W.v1;
@@ -671,16 +705,17 @@ __device__ __forceinline__ void win_stage(WinTile<AT, STEPS>& W, const YT* __res
   bool used[CPW];                                              // unused chunks are not written: the pattern record may sit there
   KK_UNROLL
   for (int i = 0; i < CPW; ++i) {
-    const int c   = wave + i * (kBlock / 64);
-    const int col = c < CAPC ? __shfl(meta, 2 * kWinCount + c, 64) : -1;            // wave-uniform
+    const int c   = PAT ? wave * CPW + i : wave + i * (kBlock / 64);                // the LDS slot of chunk c is c * 64 in both orders
+    const int col = PAT ? W.ccol[i] : c < CAPC ? __shfl(meta, 2 * kWinCount + c, 64) : -1;   // wave-uniform
     used[i]       = col >= 0;
+    if (PAT) { xv[i] = W.xv[i]; continue; }                    // requested by win_issue
     int64_t xi    = (int64_t)(used[i] ? col : 0) + lane;
     xi            = xi < ncols ? xi : ncols - 1;
     xv[i]         = x[xi];
   }
   KK_UNROLL
   for (int i = 0; i < CPW; ++i) {
-    const int c = wave + i * (kBlock / 64);
+    const int c = PAT ? wave * CPW + i : wave + i * (kBlock / 64);
     if (used[i]) prod[c * 64 + lane] = xv[i];
   }
   int* sseg = reinterpret_cast<int*>(prod + TILE) - kPatW;     // the record sits behind the x window (the analysis leaves room)
@@ -867,12 +902,15 @@ template <class YT> __device__ __forceinline__ YT strided_lds_sum(const YT* prod
 }
 
 // The planned kernel (nnz-split tiles).  What bounds a kernel that needs ~100 KB in flight per CU is the DEPENDENCY CHAIN
-// each tile goes through, so the order of issue is: (1) the tile descriptor (first row + "starts inside a row" flag: one scalar
-// load); (2) what depends on the tile index alone -- window meta, pattern record, then the value stream (with codes / entries
-// where the mode has them); (3) the per-lane row bounds row_map[r], row_map[r+1] and, for beta != 0, the old y, which need the
-// descriptor but nothing from memory; (4) a counted wait for the meta alone, then the x chunks (staged modes), or for the columns,
-// then the x gathers (plain / code tiles).  No vector-memory wait comes before the whole stream is in flight, and a staged tile
-// sees one scalar and two vector-memory latencies (stream, then x chunks).  That holds only while every load of (2) and (3) is
+// each tile goes through, so the order of issue is: (1) the kernel arguments; (2) pattern tiles: the wave's eight x chunk columns
+// (one scalar load, one scalar wait) and the x chunks; (3) what else depends on the tile index alone -- pattern record, then the value
+// stream (with window meta, codes / entries where the mode has them); (4) the tile descriptor (first row + "starts inside a row"
+// flag: one scalar load) and with it the per-lane row bounds row_map[r], row_map[r+1] and, for beta != 0, the old y, which need
+// the descriptor but nothing from memory; (5) one vector-memory wait.  A pattern tile sees two scalar-cache reads and ONE
+// vector-memory latency -- x is in LDS and the x pick under way while the values arrive --, and where its mode's tiles are
+// 0 ... n - 1 (list == null: the plan's list_identity) no list word in front.  Staged tiles without a record wait (counted) for
+// their vector meta before the x chunks, plain / code tiles for the columns before the x gathers: two vector-memory latencies.
+// No vector-memory wait comes before the whole stream is in flight.  That holds only while every load of (2) to (4) is
 // UNCONDITIONAL and its result is not touched before its real use: the row bounds are loaded with the row clamped into the
 // tile's legal range, kept as the raw loaded words, and validity, widening and the clamps to the tile are applied after the
 // barrier, where i0 / i1 are formed (a load inside `if (valid)` followed by a widening makes the compiler drain vmcnt at the
@@ -882,7 +920,7 @@ template <class YT> __device__ __forceinline__ YT strided_lds_sum(const YT* prod
 // its columns from the plan's 16-bit window codes, kTileStaged also stages the tile's x ranges in LDS (win_issue / win_stage),
 // kTilePattern decodes a row-pattern record and reads no per-nonzero code at all.  One tile the codes cannot cover costs
 // that tile its codes, not the matrix.  Each mode is its own instantiation (MODE) launched over the plan's LIST of the
-// tiles of that mode (null = every tile): one kernel with all four paths needs 135-152 registers per work-item where the
+// tiles of that mode (null = the tiles 0 ... n - 1): one kernel with all four paths needs 135-152 registers per work-item where the
 // pattern path alone needs 88, i.e. three instead of five workgroups per CU for the tiles that matter.
 template <class OffT, class AT, class YT, int NPT, int MODE>
 __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const OffT* __restrict__ row_map,
@@ -903,6 +941,9 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
   __shared__ YT prod[TILE];
   constexpr bool NT = false;
   const int t       = threadIdx.x;
+  if (MODE == kTilePattern) {                                  // every kernel argument arrives with the first scalar wait, none behind the stream
+    KK_USE_SCALAR_AFTER_ISSUE(alpha); KK_USE_SCALAR_AFTER_ISSUE(beta); KK_USE_SCALAR_AFTER_ISSUE(ncols);
+  }
   const int64_t pos = xcd_order(blockIdx.x, gridDim.x, remap);
   const int64_t b   = list ? (int64_t)list[pos] : pos;         // the plan's list of the tiles of this mode (ascending), or every tile
   const int64_t s = b * TILE;
@@ -916,12 +957,12 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
 
   AT v0[STEPS], v1[STEPS];
   int c0[STEPS], c1[STEPS];
-  WinTile<AT, STEPS> W;
+  WinTile<AT, YT, STEPS> W;
   if (MODE == kTilePattern) {                                   // records exist for full tiles only (the ragged last tile keeps its codes)
-    win_issue<AT, STEPS, true, NT, true>(values, wtile, wmeta, pmeta, b, s, e, t, W);
+    win_issue<AT, YT, STEPS, true, NT, true>(values, wtile, wmeta, pmeta, x, ncols, b, s, e, t, W);
   } else if (MODE == kTileStaged) {
-    if (full) win_issue<AT, STEPS, true, NT, false>(values, wtile, wmeta, pmeta, b, s, e, t, W);
-    else      win_issue<AT, STEPS, false, NT, false>(values, wtile, wmeta, pmeta, b, s, e, t, W);
+    if (full) win_issue<AT, YT, STEPS, true, NT, false>(values, wtile, wmeta, pmeta, x, ncols, b, s, e, t, W);
+    else      win_issue<AT, YT, STEPS, false, NT, false>(values, wtile, wmeta, pmeta, x, ncols, b, s, e, t, W);
   } else if (MODE == kTileCodes) {
     if (full) load_tile_win<AT, STEPS, true>(values, wtile, wmeta, b, s, e, t, v0, v1, c0, c1);
     else      load_tile_win<AT, STEPS, false>(values, wtile, wmeta, b, s, e, t, v0, v1, c0, c1);
@@ -1550,7 +1591,7 @@ static int analyse(kkamd_spmv_plan* p, const kkamd_crs_t* A, hipStream_t st) {
 static void free_analysis(kkamd_spmv_plan* p) {
   void** bufs[] = {(void**)&p->d_blk_row, &p->d_carry, (void**)&p->d_tinfo, (void**)&p->d_wcode, (void**)&p->d_wbase, (void**)&p->d_pmeta};
   for (void** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-  for (int m = 0; m < 4; ++m) { if (p->d_list[m]) { (void)hipFree(p->d_list[m]); p->d_list[m] = nullptr; } p->n_mode[m] = 0; }
+  for (int m = 0; m < 4; ++m) { if (p->d_list[m]) { (void)hipFree(p->d_list[m]); p->d_list[m] = nullptr; } p->n_mode[m] = 0; p->list_identity[m] = false; }
   p->pat_tiles = p->code_tiles = p->staged_tiles = p->plain_tiles = 0; p->pat_direct = false;
   p->tile = 0; p->nblocks = 0; p->plan_bytes = 0;
 }
@@ -1566,7 +1607,7 @@ static int build_codes(kkamd_spmv_plan* p, const kkamd_crs_t* A, hipStream_t st,
     (void)hipGetLastError();
     if (p->d_pmeta) { (void)hipFree(p->d_pmeta); p->d_pmeta = nullptr; }
     if (p->d_wcode) { (void)hipFree(p->d_wcode); p->d_wcode = nullptr; }
-    for (int m = 0; m < 4; ++m) { if (p->d_list[m]) { (void)hipFree(p->d_list[m]); p->d_list[m] = nullptr; } p->n_mode[m] = 0; }
+    for (int m = 0; m < 4; ++m) { if (p->d_list[m]) { (void)hipFree(p->d_list[m]); p->d_list[m] = nullptr; } p->n_mode[m] = 0; p->list_identity[m] = false; }
     p->d_tinfo = nullptr; p->d_wbase = nullptr;
     p->pat_tiles = p->code_tiles = p->staged_tiles = 0; p->plain_tiles = p->nblocks;
     p->win_failed = true;
@@ -1585,12 +1626,15 @@ static int build_codes(kkamd_spmv_plan* p, const kkamd_crs_t* A, hipStream_t st,
   KK_HIP(hipMemsetAsync(counts.p, 0, 12 * sizeof(int), st));
   const int allow_stage = p->tune.window_codes != 2;
   const int32_t* ent = (const int32_t*)p->entries;
-  // the launch lists: the tiles of every mode, ascending (none needed when one mode has every tile).  known[m] >= 0: the count of mode m is
-  // known already (no scan, no copy back for the modes without tiles).  Returns -1 when a launch or an allocation fails.
+  // the launch lists: the tiles of every mode, ascending.  None is needed when the tiles of a mode are 0 ... count - 1 (one mode has every tile,
+  // or every tile but the last ones: the workgroup index is the tile then, and the kernel has no list word to wait for) -- decided here from
+  // the scan (as many tiles of the mode among the first `count` as there are in all) and kept as list_identity[m].  known[m] >= 0: the count
+  // of mode m is known already (no scan for the modes without tiles).  Returns -1 when a launch or an allocation fails.
   auto make_lists = [&](const int64_t* known, size_t* list_bytes) -> int {
     for (int m = 0; m < 4; ++m) {
+      p->list_identity[m] = false;
       if (known && known[m] == 0) { p->n_mode[m] = 0; continue; }
-      if (known && known[m] == (int64_t)nb) { p->n_mode[m] = (int64_t)nb; continue; }
+      if (known && known[m] == (int64_t)nb) { p->n_mode[m] = (int64_t)nb; p->list_identity[m] = true; continue; }
       KK_LAUNCH(mode_flag_kernel, (unsigned)ceil_div((int64_t)nb + 1, kBlock), kBlock, 0, st, (int64_t)nb, (const int32_t*)tinfo, d_flag, m);
       if (hipGetLastError() != hipSuccess) return -1;
       int rc2 = exclusive_scan_inplace<int32_t>(d_flag, (int64_t)nb + 1, st);
@@ -1602,7 +1646,15 @@ static int build_codes(kkamd_spmv_plan* p, const kkamd_crs_t* A, hipStream_t st,
         KK_HIP(hipStreamSynchronize(st));
       }
       p->n_mode[m] = cnt;
-      if (cnt > 0 && (size_t)cnt < nb) {
+      if (cnt > 0) {
+        int32_t lead = cnt;                                      // tiles of mode m among the first cnt (the scan is exclusive)
+        if ((size_t)cnt < nb) {
+          KK_HIP(hipMemcpyAsync(&lead, d_flag + cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+          KK_HIP(hipStreamSynchronize(st));
+        }
+        p->list_identity[m] = lead == cnt;
+      }
+      if (cnt > 0 && !p->list_identity[m]) {
         if (hipMalloc((void**)&p->d_list[m], sizeof(int32_t) * (size_t)cnt) != hipSuccess) return -1;
         *list_bytes += sizeof(int32_t) * (size_t)cnt;
         int32_t* d_list_m = p->d_list[m];
@@ -2007,6 +2059,7 @@ int kkamd_spmv_plan_query(const kkamd_spmv_plan_t* plan, const char* key, int64_
   else if (k == "mv5_other_rows") *value = kk::mv5_plan_query(plan->mv5, 1);
   else if (k == "mv5_blocks") *value = kk::mv5_plan_query(plan->mv5, 2);
   else if (k == "mv5_fill_permille") *value = kk::mv5_plan_query(plan->mv5, 4);
+  else if (k == "pattern_list_identity") *value = (plan->d_tinfo && plan->d_pmeta && plan->n_mode[kTilePattern] > 0 && plan->list_identity[kTilePattern]) ? 1 : 0;
   else if (k == "pattern_direct") *value = plan->pat_direct ? 1 : 0;
   else if (k == "colslab") *value = plan->cs ? 1 : 0;
   else if (k == "colslab_tried") *value = plan->cs_tried ? 1 : 0;

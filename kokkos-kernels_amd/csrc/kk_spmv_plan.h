@@ -133,7 +133,8 @@ struct kkamd_spmv_plan {
   uint16_t* d_wcode = nullptr;   // [code_tiles * tile]
   int32_t* d_wbase = nullptr;    // [nblocks * 64] window meta: bases, LDS slots, x chunk columns
   int32_t* d_pmeta = nullptr;    // [nblocks * kPatW] row-pattern records (see pat_build_kernel), allocated when records are in use
-  int32_t* d_list[4] = {nullptr, nullptr, nullptr, nullptr};   // per tile mode: ascending list of its tiles (null: none, or every tile)
+  int32_t* d_list[4] = {nullptr, nullptr, nullptr, nullptr};   // per tile mode: ascending list of its tiles (null: none, or the identity)
+  bool list_identity[4] = {false, false, false, false};        // the mode's tiles are 0 ... n_mode - 1: no list, the launch passes null
   int64_t n_mode[4]  = {0, 0, 0, 0};                           // tiles per mode (the launch sizes)
   int64_t code_tiles = 0;        // tiles that read per-nonzero codes (modes 1, 2)
   int64_t staged_tiles = 0;      // tiles whose x window is staged in LDS (modes 2, 3)
