@@ -1,5 +1,5 @@
 /* kkamd.h -- C ABI of libkkamd.so: the MI355X (gfx950) native implementation of the
- * KokkosSparse::spmv / KokkosSparse::spgemm / KokkosSparse::sptrsv hot path.
+ * KokkosSparse::spmv / KokkosSparse::spgemm / KokkosSparse::sptrsv / KokkosSparse::spiluk hot path.
  *
  * This is the drop-in boundary.  It sits exactly where kokkos-kernels plugs vendor libraries in
  * today -- the "TPL specialisation" layer -- and takes what those specialisations hand over:
@@ -448,6 +448,62 @@ int kkamd_sptrsv_get(const kkamd_sptrsv_handle_t* handle, const char* key, int64
 /* to a HOST buffer of `count` int32: "level_list" (num_rows entries, 1-based levels as in the reference), "nodes_per_level" (num_levels),
  * "nodes_grouped_by_level" (num_rows) */
 int kkamd_sptrsv_export(const kkamd_sptrsv_handle_t* handle, const char* what, void* h_out, int64_t count);
+
+/* ------------------------------------------------------------------------------------------------
+ * Incomplete LU factorisation with level of fill k, ILU(k).  Replaces KokkosSparse::spiluk_symbolic / spiluk_numeric for a square
+ * CrsMatrix (sparse/src/KokkosSparse_spiluk.hpp:42-197,200-415; handle sparse/src/KokkosSparse_spiluk_handle.hpp:31-247; native
+ * symbolic loop sparse/impl/KokkosSparse_spiluk_symbolic_impl.hpp:212-418, numeric functor sparse/impl/KokkosSparse_spiluk_numeric_impl.hpp:438-551,
+ * level loop :572-617).  The factors are what kkamd_sptrsv_* takes: row i of L holds the columns < i and then the unit diagonal, row i of
+ * U the diagonal (present even when A has none) and then the columns > i, both sorted by column.  int32 ordinals, int32 or int64 offsets
+ * (one type for A, L and U), values F64 or F32.
+ *
+ * The handle is the analogue of SPILUKHandle: nnzL, nnzU, the level sets of L (level_list, level_ptr, level_idx as the reference's handle
+ * holds them) and this library's knobs, never values.  Not implemented: the block (BSR) variant, spiluk_numeric_streams, a device-side
+ * fill computation, the reference-side TPL binding.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_spiluk_handle kkamd_spiluk_handle_t;
+/* KokkosSparse::Experimental::SPILUKAlgorithm (sparse/src/KokkosSparse_spiluk_handle.hpp:31-33): the reference has one */
+typedef enum { KKAMD_SPILUK_SEQLVLSCHD_TP1 = 0 } kkamd_spiluk_algorithm;
+/* KokkosKernelsHandle::create_spiluk_handle(algm, nrows, nnzL, nnzU) / destroy_spiluk_handle (sparse/src/KokkosKernels_Handle.hpp);
+ * nnzL and nnzU are the caller's estimates, replaced by the true counts at symbolic (spiluk_handle.hpp:102-121,190-199) */
+int kkamd_spiluk_create(kkamd_spiluk_handle_t** handle, int algorithm, int64_t num_rows, int64_t nnzL, int64_t nnzU);
+int kkamd_spiluk_destroy(kkamd_spiluk_handle_t* handle);
+/* spiluk_symbolic(handle, fill_lev, A_rowmap, A_entries, L_rowmap, L_entries, U_rowmap, U_entries) (sparse/src/KokkosSparse_spiluk.hpp:42-197;
+ * sparse/impl/KokkosSparse_spiluk_symbolic_impl.hpp:212-418).  Writes the graphs of L and U for the sum-rule level of fill (entries of A
+ * have level 0; eliminating row i by pivot j, pivots ascending, gives column c of U row j the level lev(i,j) + lev(j,c) + 1, kept when
+ * <= fill_lev; an existing entry takes the minimum) and records nnzL, nnzU and the level sets of L.  L_capacity / U_capacity are the
+ * extents of d_L_entries / d_U_entries: when one is too small nothing is written and KKAMD_ERR_INVALID_ARG comes back with the reference's
+ * text "... must be larger than <capacity>, must be at least <nnz>" (:353-357,375-379) carrying the true count.  Checked before anything
+ * is indexed (KKAMD_ERR_INVALID_ARG, first offending row named): num_rows equal to the handle's, A's row map ascending, columns in
+ * [0, num_rows), no column twice in a row of A (the reference overwrites in a race there); fill_lev < 0 gives the reference's message
+ * (spiluk.hpp:127-131).  The fill computation runs on the host, as in the reference; the level sets come from the device routine of
+ * kkamd_sptrsv_symbolic.  May be repeated on one handle.  Synchronises the stream, because it returns counts. */
+int kkamd_spiluk_symbolic(kkamd_spiluk_handle_t* handle, int fill_lev, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries,
+                          void* d_L_row_map, int32_t* d_L_entries, int64_t L_capacity, void* d_U_row_map, int32_t* d_U_entries, int64_t U_capacity,
+                          int offset_type, kkamd_stream_t stream);
+/* spiluk_numeric(handle, fill_lev, A_rowmap, A_entries, A_values, L_rowmap, L_entries, L_values, U_rowmap, U_entries, U_values)
+ * (sparse/src/KokkosSparse_spiluk.hpp:200-415; sparse/impl/KokkosSparse_spiluk_numeric_impl.hpp:438-551,572-617).  KKAMD_ERR_STATE before
+ * a completed symbolic call, KKAMD_ERR_UNSUPPORTED for another value type; otherwise asynchronous on the stream: allocates nothing,
+ * synchronises nothing, reads A at every call (new values on the analysed pattern need no second symbolic call).  The old content of
+ * L_values / U_values is never read.  A zero pivot U(i,i) is replaced by 1e6 as in the reference (:528-534).  Deterministic: every entry
+ * takes its updates one pivot at a time in ascending order, whatever the knobs. */
+int kkamd_spiluk_numeric(kkamd_spiluk_handle_t* handle, int fill_lev, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries,
+                         const void* d_A_values, const void* d_L_row_map, const int32_t* d_L_entries, void* d_L_values, const void* d_U_row_map,
+                         const int32_t* d_U_entries, void* d_U_values, int offset_type, int value_type, kkamd_stream_t stream);
+/* Knobs (values outside the ranges: KKAMD_ERR_INVALID_ARG; the analogue of SPILUKHandle::set_team_size / set_vector_size,
+ * spiluk_handle.hpp:231-235), with the meaning and defaults of kkamd_sptrsv_set:
+ *   "lanes_per_row"  0 (default) = the smallest power of two that covers the mean row of U, or 1, 2, 4, ..., 64
+ *   "chain_rows"     a level with at most this many rows may join a chain; 0 = never; default 64
+ *   "chain_levels"   the most levels one chain launch covers (>= 1, default 1024) */
+int kkamd_spiluk_set(kkamd_spiluk_handle_t* handle, const char* key, int value);
+/* "nnzL", "nnzU", "num_levels", "max_level_rows", "symbolic_complete", "algorithm", "num_rows", "launches" (kernel launches of one
+ * numeric call), "chain_launches", "chained_levels", "plan_bytes" (HBM the handle keeps; at most 64 (num_rows + nnzL + nnzU) + 4096),
+ * the three knobs, "lanes_in_use", "stage_entries_per_lane" (a row of up to this many entries per lane, L and U parts together, is staged
+ * in LDS), "symbolic_fill_us" / "symbolic_other_us" (the host fill loop and the rest of the last symbolic call) */
+int kkamd_spiluk_get(const kkamd_spiluk_handle_t* handle, const char* key, int64_t* value);
+/* to a HOST buffer of `count` int32: "level_list" (num_rows entries, 1-based levels as in the reference), "level_ptr" (num_levels + 1),
+ * "level_idx" (num_rows: the rows grouped by level) */
+int kkamd_spiluk_export(const kkamd_spiluk_handle_t* handle, const char* what, void* h_out, int64_t count);
 
 /* ------------------------------------------------------------------------------------------------
  * Helpers either side of the path (KokkosSparse::sort_crs_matrix, sparse/src/KokkosSparse_SortCrs.hpp:43-120;

@@ -1,4 +1,4 @@
-"""kokkos-kernels_amd -- MI355X (gfx950) native KokkosSparse::spmv / spgemm / sptrsv hot path.
+"""kokkos-kernels_amd -- MI355X (gfx950) native KokkosSparse::spmv / spgemm / sptrsv / spiluk hot path.
 
 The product is libkkamd.so (hand-written HIP, C ABI in include/kkamd.h) plus the C++ drop-in headers
 under host/.  This Python package is plumbing for tests and benchmarks: it loads the library, keeps
@@ -65,5 +65,5 @@ def device_check():
 
 
 from .sparse import (CrsMatrix, SPMVHandle, KokkosKernelsHandle, spmv, spmv_struct, sort_and_merge_matrix, transpose_matrix, spgemm_symbolic, spgemm_numeric, spgemm,  # noqa: E402,F401
-                     sort_crs_matrix, laplace_matrix, Backend, torch_backend, sptrsv_symbolic, sptrsv_solve)
+                     sort_crs_matrix, laplace_matrix, Backend, torch_backend, sptrsv_symbolic, sptrsv_solve, spiluk_symbolic, spiluk_numeric)
 from . import io  # noqa: E402,F401  (matrix file formats: .mtx / .bin / .crs)

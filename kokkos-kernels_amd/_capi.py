@@ -7,6 +7,7 @@ I32, I64 = 0, 1
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_ALLOC, ERR_STATE = range(6)
 SPMV_DEFAULT, SPMV_FAST_SETUP, SPMV_NATIVE, SPMV_MERGE_PATH, SPMV_NATIVE_MERGE_PATH = range(5)
 SPTRSV_SEQLVLSCHD_RP, SPTRSV_SEQLVLSCHD_TP1, SPTRSV_SEQLVLSCHD_TP1CHAIN, SPTRSV_CUSPARSE = range(4)
+SPILUK_SEQLVLSCHD_TP1 = 0
 
 EXPORTS = [
     "kkamd_last_error", "kkamd_version", "kkamd_device_info", "kkamd_trace_push", "kkamd_trace_pop", "kkamd_spmv_plan_create", "kkamd_spmv_plan_create_knobs", "kkamd_release_scratch", "kkamd_spmv_plan_destroy",
@@ -21,6 +22,9 @@ EXPORTS = [
 # the sparse triangular solve: bound when the loaded library exports it (the emulator library of tests/emu/Makefile does not)
 SPTRSV_EXPORTS = ["kkamd_sptrsv_create", "kkamd_sptrsv_destroy", "kkamd_sptrsv_symbolic", "kkamd_sptrsv_solve", "kkamd_sptrsv_set",
                   "kkamd_sptrsv_get", "kkamd_sptrsv_export"]
+# ILU(k): bound when the loaded library exports it, like the triangular solve
+SPILUK_EXPORTS = ["kkamd_spiluk_create", "kkamd_spiluk_destroy", "kkamd_spiluk_symbolic", "kkamd_spiluk_numeric", "kkamd_spiluk_set",
+                  "kkamd_spiluk_get", "kkamd_spiluk_export"]
 
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int,
@@ -103,6 +107,15 @@ def bind(lib):
         lib.kkamd_sptrsv_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
         lib.kkamd_sptrsv_export.argtypes = [vp, C.c_char_p, vp, i64]
         names += SPTRSV_EXPORTS
+    if hasattr(lib, "kkamd_spiluk_create"):
+        lib.kkamd_spiluk_create.argtypes = [C.POINTER(vp), ci, i64, i64, i64]
+        lib.kkamd_spiluk_destroy.argtypes = [vp]
+        lib.kkamd_spiluk_symbolic.argtypes = [vp, ci, i64, vp, vp, vp, vp, i64, vp, vp, i64, ci, vp]
+        lib.kkamd_spiluk_numeric.argtypes = [vp, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
+        lib.kkamd_spiluk_set.argtypes = [vp, C.c_char_p, ci]
+        lib.kkamd_spiluk_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
+        lib.kkamd_spiluk_export.argtypes = [vp, C.c_char_p, vp, i64]
+        names += SPILUK_EXPORTS
     for name in names:
         fn = getattr(lib, name)
         if name == "kkamd_dist_spgemm_handle":

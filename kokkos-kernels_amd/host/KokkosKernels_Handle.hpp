@@ -1,6 +1,6 @@
-// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM and SPTRSV paths use
-// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862): create / get / destroy of the SpGEMM
-// and SPTRSV sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
+// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV and SPILUK paths use
+// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862, spiluk :853-870): create / get / destroy of the
+// SpGEMM, SPTRSV and SPILUK sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
 // decision, like KOKKOSKERNELS_VERBOSE).  The team / vector / shared-memory / scheduling setters are HINTS in the reference
 // too -- its rocSPARSE and cuSPARSE paths take and ignore them, and its driver and unit tests set them before every spgemm
 // (perf_test/sparse/KokkosSparse_spgemm.cpp:311-317, sparse/unit_test/Test_Sparse_spgemm.hpp:91-92) -- so they are accepted,
@@ -9,6 +9,7 @@
 #pragma once
 #include "KokkosSparse_spgemm_handle.hpp"
 #include "KokkosSparse_sptrsv_handle.hpp"
+#include "KokkosSparse_spiluk_handle.hpp"
 
 namespace KokkosKernels { namespace Experimental {
 
@@ -29,8 +30,10 @@ class KokkosKernelsHandle {
                                                      TemporaryMemorySpace, PersistentMemorySpace>;
   using SPTRSVHandleType = KokkosSparse::Experimental::SPTRSVHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace,
                                                                    TemporaryMemorySpace, PersistentMemorySpace>;
+  using SPILUKHandleType = KokkosSparse::Experimental::SPILUKHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace,
+                                                                   TemporaryMemorySpace, PersistentMemorySpace>;
   KokkosKernelsHandle() = default;
-  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); }
+  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); }
   KokkosKernelsHandle(const KokkosKernelsHandle&)            = delete;
   KokkosKernelsHandle& operator=(const KokkosKernelsHandle&) = delete;
 
@@ -59,6 +62,17 @@ class KokkosKernelsHandle {
   void destroy_sptrsv_handle() { delete sptrsv_; sptrsv_ = nullptr; }
   bool is_sptrsv_lower_tri() { return sptrsv_->is_lower_tri(); }
 
+  // SPILUK sub-handle (:853-870); nnzL and nnzU are the caller's estimates until the symbolic phase sets the true counts
+  SPILUKHandleType* get_spiluk_handle() { return spiluk_; }
+  void create_spiluk_handle(KokkosSparse::Experimental::SPILUKAlgorithm algm, size_type nrows, size_type nnzL, size_type nnzU,
+                            size_type block_size = 0) {
+    destroy_spiluk_handle();
+    spiluk_ = new SPILUKHandleType(algm, nrows, nnzL, nnzU, block_size);
+    spiluk_->set_team_size(team_work_size);
+    spiluk_->set_vector_size(vector_size);
+  }
+  void destroy_spiluk_handle() { delete spiluk_; spiluk_ = nullptr; }
+
   // hints of the reference (:380-465; defaults :203-215): remembered, forwarded, without effect on gfx950
   void set_team_work_size(const int v) { team_work_size = v; hint("team_work_size", v); }
   int get_set_team_work_size() { return team_work_size; }
@@ -84,6 +98,7 @@ class KokkosKernelsHandle {
   bool use_dynamic_scheduling = true;
   SPGEMMHandleType* spgemm_ = nullptr;
   SPTRSVHandleType* sptrsv_ = nullptr;
+  SPILUKHandleType* spiluk_ = nullptr;
   bool verbose_             = false;
 };
 

@@ -322,6 +322,7 @@ class KokkosKernelsHandle:
         self.backend = backend
         self._spgemm = None
         self._sptrsv = None
+        self._spiluk = None
 
     def create_spgemm_handle(self, algo="SPGEMM_KK"):
         """algo: a KokkosSparse::SPGEMMAlgorithm name (sparse/src/KokkosSparse_spgemm_handle.hpp:44-93).  SPGEMM_DEBUG / SPGEMM_SERIAL
@@ -355,6 +356,22 @@ class KokkosKernelsHandle:
         if self._sptrsv is not None:
             self._sptrsv.destroy()
         self._sptrsv = None
+
+    def create_spiluk_handle(self, algo, nrows, nnzL, nnzU):
+        """create_spiluk_handle(algm, nrows, nnzL, nnzU) (sparse/src/KokkosKernels_Handle.hpp:853-870); algo: a
+        KokkosSparse::Experimental::SPILUKAlgorithm name (sparse/src/KokkosSparse_spiluk_handle.hpp:31-33)"""
+        self.backend = self.backend or torch_backend()
+        if algo not in _SPILUK_ALGOS:
+            raise RuntimeError("Invalid SPILUKAlgorithm name")
+        self.destroy_spiluk_handle()
+        self._spiluk = _SpilukHandle(self.backend, algo, nrows, nnzL, nnzU)
+
+    def get_spiluk_handle(self): return self._spiluk
+
+    def destroy_spiluk_handle(self):
+        if self._spiluk is not None:
+            self._spiluk.destroy()
+        self._spiluk = None
 
 
 _SPTRSV_ALGOS = {"SEQLVLSCHD_RP": 0, "SEQLVLSCHD_TP1": 1, "SEQLVLSCHD_TP1CHAIN": 2, "SPTRSV_CUSPARSE": 3}
@@ -441,6 +458,99 @@ def sptrsv_solve(kh, row_map, entries, values, b, x):
             raise ValueError(str(e))   # std::invalid_argument in the reference
         raise
     return x
+
+
+_SPILUK_ALGOS = {"SEQLVLSCHD_TP1": 0}
+
+
+class _SpilukHandle:
+    """KokkosSparse::Experimental::SPILUKHandle as far as the level-scheduled factorisation uses it
+    (sparse/src/KokkosSparse_spiluk_handle.hpp): algorithm, size, nnzL and nnzU, the level sets of L, and this library's knobs."""
+
+    def __init__(self, backend, algo, nrows, nnzL, nnzU):
+        self.backend, self.algo = backend, algo
+        self.h = C.c_void_p()
+        check(backend.lib, backend.lib.kkamd_spiluk_create(C.byref(self.h), _SPILUK_ALGOS[algo], int(nrows), int(nnzL), int(nnzU)))
+
+    def set(self, key, value):
+        """"lanes_per_row", "chain_rows", "chain_levels" (kkamd_spiluk_set)"""
+        check(self.backend.lib, self.backend.lib.kkamd_spiluk_set(self.h, key.encode(), int(value)))
+
+    def get(self, key):
+        v = C.c_int64()
+        check(self.backend.lib, self.backend.lib.kkamd_spiluk_get(self.h, key.encode(), C.byref(v)))
+        return int(v.value)
+
+    def export(self, what):
+        """"level_list" (1-based), "level_ptr" (num_levels + 1) or "level_idx" as a host int32 array"""
+        n = self.get("num_levels") + 1 if what == "level_ptr" else self.get("num_rows")
+        out = np.zeros(n, dtype=np.int32)
+        check(self.backend.lib, self.backend.lib.kkamd_spiluk_export(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def get_algorithm(self): return self.algo
+    def get_nrows(self): return self.get("num_rows")
+    def get_nnzL(self): return self.get("nnzL")
+    def get_nnzU(self): return self.get("nnzU")
+    def get_num_levels(self): return self.get("num_levels")
+    def is_symbolic_complete(self): return bool(self.get("symbolic_complete"))
+
+    def destroy(self):
+        if self.h:
+            self.backend.lib.kkamd_spiluk_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _spiluk_handle(kh, who):
+    ih = kh.get_spiluk_handle() if kh is not None else None
+    if ih is None:
+        raise ValueError("KokkosSparse::%s: the given KernelHandle does not have an SPILUK handle associated with it." % who)
+    return ih
+
+
+def spiluk_symbolic(kh, fill_lev, A_row_map, A_entries, L_row_map, L_entries, U_row_map, U_entries):
+    """KokkosSparse::spiluk_symbolic(handle, fill_lev, A_rowmap, A_entries, L_rowmap, L_entries, U_rowmap, U_entries)
+    (sparse/src/KokkosSparse_spiluk.hpp:42-197): writes the graphs of L and U for level of fill fill_lev and records nnzL, nnzU and the
+    level sets of L in the handle.  The extents of L_entries / U_entries are the capacities.  May be repeated."""
+    ih = _spiluk_handle(kh, "spiluk_symbolic")
+    be, lib = ih.backend, ih.backend.lib
+    n = int(A_row_map.shape[0]) - 1
+    if L_row_map.shape[0] != n + 1 or U_row_map.shape[0] != n + 1:
+        raise RuntimeError("KokkosSparse::spiluk_symbolic: L_rowmap and U_rowmap must have A_rowmap's extent %d" % (n + 1))
+    if _np_dtype(L_row_map) != _np_dtype(A_row_map) or _np_dtype(U_row_map) != _np_dtype(A_row_map):
+        raise RuntimeError("KokkosSparse::spiluk_symbolic: A_rowmap, L_rowmap and U_rowmap must have one offset type")
+    check(lib, lib.kkamd_spiluk_symbolic(ih.h, int(fill_lev), n, be.ptr(A_row_map), be.ptr(A_entries), be.ptr(L_row_map), be.ptr(L_entries),
+                                         int(L_entries.shape[0]), be.ptr(U_row_map), be.ptr(U_entries), int(U_entries.shape[0]),
+                                         _offset_type(A_row_map), be.stream()))
+
+
+def spiluk_numeric(kh, fill_lev, A_row_map, A_entries, A_values, L_row_map, L_entries, L_values, U_row_map, U_entries, U_values):
+    """KokkosSparse::spiluk_numeric(handle, fill_lev, A_rowmap, A_entries, A_values, L_rowmap, L_entries, L_values, U_rowmap, U_entries,
+    U_values) (sparse/src/KokkosSparse_spiluk.hpp:200-415): the ILU(k) factors of A on the analysed pattern, on the backend's current
+    stream.  New values of A need no second symbolic call."""
+    ih = _spiluk_handle(kh, "spiluk_numeric")
+    be, lib = ih.backend, ih.backend.lib
+    n = int(A_row_map.shape[0]) - 1
+    if _np_dtype(L_values) != _np_dtype(A_values) or _np_dtype(U_values) != _np_dtype(A_values):
+        raise RuntimeError("KokkosSparse::spiluk_numeric: A_values, L_values and U_values must have one scalar type")
+    if _np_dtype(L_row_map) != _np_dtype(A_row_map) or _np_dtype(U_row_map) != _np_dtype(A_row_map):
+        raise RuntimeError("KokkosSparse::spiluk_numeric: A_rowmap, L_rowmap and U_rowmap must have one offset type")
+    if ih.is_symbolic_complete() and (L_values.shape[0] < ih.get_nnzL() or U_values.shape[0] < ih.get_nnzU()):
+        raise RuntimeError("KokkosSparse::spiluk_numeric: L_values / U_values are shorter than nnzL / nnzU")
+    try:
+        check(lib, lib.kkamd_spiluk_numeric(ih.h, int(fill_lev), n, be.ptr(A_row_map), be.ptr(A_entries), be.ptr(A_values), be.ptr(L_row_map),
+                                            be.ptr(L_entries), be.ptr(L_values), be.ptr(U_row_map), be.ptr(U_entries), be.ptr(U_values),
+                                            _offset_type(A_row_map), _scalar_type(A_values), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))   # std::invalid_argument in the reference
+        raise
 
 
 def spgemm_symbolic(kh, A, transposeA, B, transposeB, Cmat=None, allocate=True):

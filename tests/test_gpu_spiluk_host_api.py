@@ -1,0 +1,26 @@
+"""Runs the C++ drop-in header test of ILU(k) (kokkos-kernels_amd/host/tests/test_spiluk_drop_in.cpp) on the GPU:
+KokkosSparse::spiluk_symbolic / spiluk_numeric over KokkosKernelsHandle::create_spiluk_handle at fill levels 0 and 2 against factors
+computed in the program, a resize to get_nnzL() / get_nnzU() after the symbolic phase, the too-small-extent exception, and the
+KokkosSparse::Experimental:: names."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "kokkos-kernels_amd", "host", "tests", "test_spiluk_drop_in")
+
+
+@pytest.mark.gpu
+def test_cpp_spiluk_drop_in_headers():
+    assert os.path.exists(EXE), "build it with __graft_entry__.build() (make -C kokkos-kernels_amd/host)"
+    r = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all passed" in r.stdout
+
+
+def test_cpp_spiluk_drop_in_headers_build():
+    """CPU-side: the headers compile and link against libkkamd.so (no GPU needed to build)."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "kokkos-kernels_amd", "host"), "-s", "tests/test_spiluk_drop_in"])
+    assert os.path.exists(EXE)
