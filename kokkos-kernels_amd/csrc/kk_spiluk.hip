@@ -4,8 +4,8 @@
 // Symbolic phase (sparse/impl/KokkosSparse_spiluk_symbolic_impl.hpp:212-418).  As in the reference the fill computation runs on the
 // host: the graph of A is copied down, validated before anything is indexed by it, run through the reference's sum-rule loop
 // (kk_spiluk_fill.h) and the graphs of L and U are copied up.  It runs once per pattern.  The level sets are those of L (:400-402):
-// level(i) = 1 + max level(col) over the off-diagonal columns of L row i, rows ascending inside a level.  That is the definition
-// kk_sptrsv.hip implements on the device, so they come from an internal sptrsv handle analysed on L.
+// level(i) = 1 + max level(col) over the off-diagonal columns of L row i, rows ascending inside a level.  That is what the analysis
+// of the triangular solve computes on the device (kk_sptrsv.hip): it runs on L, and the handle keeps the schedule it fills.
 //
 // Numeric phase (sparse/impl/KokkosSparse_spiluk_numeric_impl.hpp:438-551, level loop :572-617).  One launch per level; a group of
 // LPR lanes owns one row i:
@@ -22,13 +22,12 @@
 // No work-item ever waits on another workgroup: every dependency between workgroups is a kernel boundary on the stream.
 //
 // Not here: the block (BSR) variant, spiluk_numeric_streams, a device-side fill computation, the reference-side TPL binding.
-#include "kk_common.h"
+#include "kk_levels.h"
 #include "kk_spiluk_fill.h"
 #include <chrono>
 #include <climits>
 #include <cstring>
 #include <new>
-#include <vector>
 
 // Orders one lane group's memory operations between two steps of a row: what a lane stored before it (LDS or global memory) is
 // visible to the loads of the other lanes after it.  Release and acquire fences at workgroup scope around the wave barrier; nothing
@@ -169,78 +168,34 @@ __global__ __launch_bounds__(kBlock) void spiluk_chain_kernel(const int32_t* __r
   }
 }
 
-struct SpilukLaunch {
-  int first, nlev;      // levels covered
-  int chain;
-};
-
 }  // namespace kk
 
 struct kkamd_spiluk_handle {
   int algorithm = 0;
   int64_t nrows = 0, nnzL = 0, nnzU = 0;
-  int lanes_per_row = 0, chain_rows = 64, chain_levels = 1024;
   bool symbolic_complete = false;
-  int32_t* d_grouped = nullptr;
-  int64_t* d_level_off = nullptr;
+  kk::LevelSchedule sched;                                 // of L
   std::vector<int32_t> level_list, level_ptr, level_idx;  // host, as the reference's handle holds them (level_list 1-based)
-  std::vector<int64_t> level_off;                          // host: level_ptr in 64 bits
-  std::vector<kk::SpilukLaunch> plan;                      // the launches of one numeric call
-  int64_t max_level_rows = 0, chain_launches = 0, chained_levels = 0;
   int64_t fill_us = 0, levels_us = 0;                      // host fill loop; everything else of the last symbolic call
 
-  void free_device() {
-    if (d_grouped) (void)hipFree(d_grouped);
-    if (d_level_off) (void)hipFree(d_level_off);
-    d_grouped = nullptr;
-    d_level_off = nullptr;
-  }
-  int64_t num_levels() const { return level_off.empty() ? 0 : (int64_t)level_off.size() - 1; }
   void clear_symbolic() {
     symbolic_complete = false;
-    free_device();
-    level_list.clear(); level_ptr.clear(); level_idx.clear(); level_off.clear(); plan.clear();
-    max_level_rows = chain_launches = chained_levels = 0;
+    sched.clear();
+    level_list.clear(); level_ptr.clear(); level_idx.clear();
   }
 };
 
 namespace kk {
 
-static int spiluk_log2i(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
-
-// the rule of kk_sptrsv.hip's lanes_for on the mean row of U: the smallest power of two, 1..64, that covers it
+// one lane count for every launch: what covers the mean row of U
 static int spiluk_lanes(const kkamd_spiluk_handle* h) {
-  if (h->lanes_per_row) return h->lanes_per_row;
-  const int64_t mean = h->nrows > 0 ? ceil_div(h->nnzU, h->nrows) : 1;
-  int lpr = 1;
-  while (lpr < kWave && lpr < mean) lpr *= 2;
-  return lpr;
+  return h->sched.lanes_per_row ? h->sched.lanes_per_row : pow2_covering(h->nrows > 0 ? ceil_div(h->nnzU, h->nrows) : 1);
 }
 
-// the launches of one numeric call from the level sizes and the knobs: one per level, except that every run of two or more
-// consecutive levels with at most chain_rows rows each goes into ceil(run / chain_levels) chain launches
+// the launches of one numeric call; every set builds them again, so the lane count stored with each stays right
 static void spiluk_build_plan(kkamd_spiluk_handle* h) {
-  h->plan.clear();
-  h->chain_launches = h->chained_levels = 0;
-  const int64_t L = h->num_levels();
-  int64_t l = 0;
-  while (l < L) {
-    int64_t run = 0;
-    if (h->chain_rows > 0)
-      while (l + run < L && h->level_off[l + run + 1] - h->level_off[l + run] <= h->chain_rows) ++run;
-    if (run < 2) {
-      h->plan.push_back({(int)l, 1, 0});
-      ++l;
-      continue;
-    }
-    for (int64_t p = 0; p < run; p += h->chain_levels) {
-      const int64_t nl = run - p < h->chain_levels ? run - p : h->chain_levels;
-      h->plan.push_back({(int)(l + p), (int)nl, 1});
-      h->chain_launches += 1;
-      h->chained_levels += nl;
-    }
-    l += run;
-  }
+  const int lpr = spiluk_lanes(h);
+  build_plan(&h->sched, h->sched.chain_rows > 0, [lpr](int64_t, int64_t) { return lpr; });
 }
 
 template <class OffT>
@@ -286,36 +241,21 @@ static int spiluk_symbolic_typed(kkamd_spiluk_handle* h, int fill_lev, int64_t n
   if (nnzL > 0) KK_HIP(hipMemcpyAsync(L_ent, pat.L_ent.data(), sizeof(int32_t) * (size_t)nnzL, hipMemcpyHostToDevice, st));
   if (nnzU > 0) KK_HIP(hipMemcpyAsync(U_ent, pat.U_ent.data(), sizeof(int32_t) * (size_t)nnzU, hipMemcpyHostToDevice, st));
   KK_HIP(hipStreamSynchronize(st));                          // the host vectors go out of use
-  // the level sets of L, by the device routine of the triangular solve
-  kkamd_sptrsv_handle_t* th = nullptr;
-  int rc = kkamd_sptrsv_create(&th, KKAMD_SPTRSV_SEQLVLSCHD_TP1, n, 1);
-  if (rc) return rc;
-  rc = kkamd_sptrsv_symbolic(th, n, L_rm, L_ent, offset_type, reinterpret_cast<kkamd_stream_t>(st));
-  int64_t nlev = 0;
-  if (!rc) rc = kkamd_sptrsv_get(th, "num_levels", &nlev);
-  std::vector<int32_t> per_level((size_t)nlev);
+  // the level sets of L: the schedule stays as the analysis leaves it; level_list and the diagonal positions are not kept on the device
+  DevBuf list_b, diag_b;
+  {
+    TraceRange levels("KokkosSparse::sptrsv_symbolic[TPL_KKAMD]");
+    const int rc = analyse_levels(&h->sched, n, 1, L_rm, L_ent, offset_type, st, &list_b, &diag_b);
+    if (rc) return rc;
+  }
   h->level_list.assign((size_t)n, 0);
   h->level_idx.assign((size_t)n, 0);
-  if (!rc) rc = kkamd_sptrsv_export(th, "level_list", h->level_list.data(), n);
-  if (!rc) rc = kkamd_sptrsv_export(th, "nodes_grouped_by_level", h->level_idx.data(), n);
-  if (!rc) rc = kkamd_sptrsv_export(th, "nodes_per_level", per_level.data(), nlev);
-  (void)kkamd_sptrsv_destroy(th);
-  if (rc) return rc;
-  h->level_off.assign((size_t)nlev + 1, 0);
-  h->level_ptr.assign((size_t)nlev + 1, 0);
-  for (int64_t l = 0; l < nlev; ++l) {
-    h->level_off[(size_t)l + 1] = h->level_off[(size_t)l] + per_level[(size_t)l];
-    h->level_ptr[(size_t)l + 1] = (int32_t)h->level_off[(size_t)l + 1];
-    if (per_level[(size_t)l] > h->max_level_rows) h->max_level_rows = per_level[(size_t)l];
+  if (n > 0) {
+    KK_HIP(hipMemcpyAsync(h->level_list.data(), list_b.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    KK_HIP(hipMemcpyAsync(h->level_idx.data(), h->sched.d_grouped, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    KK_HIP(hipStreamSynchronize(st));
   }
-  DevBuf grouped_b, off_b;
-  KK_HIP(grouped_b.alloc(sizeof(int32_t) * (size_t)n));
-  KK_HIP(off_b.alloc(sizeof(int64_t) * (size_t)(nlev + 1)));
-  KK_HIP(hipMemcpyAsync(grouped_b.p, h->level_idx.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  KK_HIP(hipMemcpyAsync(off_b.p, h->level_off.data(), sizeof(int64_t) * (size_t)(nlev + 1), hipMemcpyHostToDevice, st));
-  KK_HIP(hipStreamSynchronize(st));
-  h->d_grouped   = (int32_t*)grouped_b.release();
-  h->d_level_off = (int64_t*)off_b.release();
+  h->level_ptr.assign(h->sched.level_off.begin(), h->sched.level_off.end());   // offsets up to n < 2^31
   h->nnzL = nnzL;
   h->nnzU = nnzU;
   const auto t3 = clock::now();
@@ -327,14 +267,15 @@ static int spiluk_symbolic_typed(kkamd_spiluk_handle* h, int fill_lev, int64_t n
 template <class OffT, class VT>
 static int spiluk_numeric_typed(const kkamd_spiluk_handle* h, const OffT* A_rm, const int32_t* A_ent, const VT* A_val, const OffT* L_rm,
                                 const int32_t* L_ent, VT* L_val, const OffT* U_rm, const int32_t* U_ent, VT* U_val, hipStream_t st) {
-  const int lpr = spiluk_lanes(h), sh = spiluk_log2i(lpr);
-  for (const SpilukLaunch& q : h->plan) {
+  const LevelSchedule& s = h->sched;
+  for (const LevelLaunch& q : s.plan) {
+    const int sh = log2i(q.lpr);
     if (q.chain) {
-      KK_LAUNCH((spiluk_chain_kernel<OffT, VT>), 1u, kBlock, 0, st, (const int32_t*)h->d_grouped, (const int64_t*)h->d_level_off, q.first, q.nlev, lpr, sh,
+      KK_LAUNCH((spiluk_chain_kernel<OffT, VT>), 1u, kBlock, 0, st, (const int32_t*)s.d_grouped, (const int64_t*)s.d_level_off, q.first, q.nlev, q.lpr, sh,
                 A_rm, A_ent, A_val, L_rm, L_ent, L_val, U_rm, U_ent, U_val);
     } else {
-      const int64_t beg = h->level_off[q.first], cnt = h->level_off[q.first + 1] - beg;
-      KK_LAUNCH((spiluk_level_kernel<OffT, VT>), (unsigned)ceil_div(cnt * lpr, kBlock), kBlock, 0, st, (const int32_t*)(h->d_grouped + beg), cnt, lpr, sh,
+      const int64_t beg = s.level_off[q.first], cnt = s.level_off[q.first + 1] - beg;
+      KK_LAUNCH((spiluk_level_kernel<OffT, VT>), (unsigned)ceil_div(cnt * q.lpr, kBlock), kBlock, 0, st, (const int32_t*)(s.d_grouped + beg), cnt, q.lpr, sh,
                 A_rm, A_ent, A_val, L_rm, L_ent, L_val, U_rm, U_ent, U_val);
     }
   }
@@ -365,7 +306,7 @@ int kkamd_spiluk_create(kkamd_spiluk_handle_t** handle, int algorithm, int64_t n
 
 int kkamd_spiluk_destroy(kkamd_spiluk_handle_t* h) {
   if (!h) return KKAMD_OK;
-  h->free_device();
+  h->sched.clear();
   delete h;
   return KKAMD_OK;
 }
@@ -428,19 +369,8 @@ int kkamd_spiluk_numeric(kkamd_spiluk_handle_t* h, int fill_lev, int64_t num_row
 
 int kkamd_spiluk_set(kkamd_spiluk_handle_t* h, const char* key, int value) {
   if (!h || !key) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_set: null argument");
-  const std::string k(key);
-  if (k == "lanes_per_row") {
-    if (value < 0 || value > kk::kWave || (value & (value - 1))) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_set: lanes_per_row %d is not 0 or a power of two up to 64", value);
-    h->lanes_per_row = value;
-  } else if (k == "chain_rows") {
-    if (value < 0) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_set: chain_rows %d is negative", value);
-    h->chain_rows = value;
-  } else if (k == "chain_levels") {
-    if (value < 1) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_set: chain_levels %d is below 1", value);
-    h->chain_levels = value;
-  } else {
-    return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_set: unknown key '%s'", key);
-  }
+  const int rc = kk::set_knob(&h->sched, "kkamd_spiluk_set", key, value);
+  if (rc) return rc;
   if (h->symbolic_complete) kk::spiluk_build_plan(h);
   return KKAMD_OK;
 }
@@ -448,25 +378,18 @@ int kkamd_spiluk_set(kkamd_spiluk_handle_t* h, const char* key, int value) {
 int kkamd_spiluk_get(const kkamd_spiluk_handle_t* h, const char* key, int64_t* value) {
   if (!h || !key || !value) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_get: null argument");
   const std::string k(key);
+  if (kk::get_common(h->sched, k, value)) return KKAMD_OK;
   if (k == "nnzL") *value = h->nnzL;
   else if (k == "nnzU") *value = h->nnzU;
-  else if (k == "num_levels") *value = h->num_levels();
-  else if (k == "max_level_rows") *value = h->max_level_rows;
   else if (k == "symbolic_complete") *value = h->symbolic_complete ? 1 : 0;
   else if (k == "algorithm") *value = h->algorithm;
   else if (k == "num_rows") *value = h->nrows;
-  else if (k == "launches") *value = (int64_t)h->plan.size();
-  else if (k == "chain_launches") *value = h->chain_launches;
-  else if (k == "chained_levels") *value = h->chained_levels;
-  else if (k == "lanes_per_row") *value = h->lanes_per_row;
-  else if (k == "chain_rows") *value = h->chain_rows;
-  else if (k == "chain_levels") *value = h->chain_levels;
   else if (k == "lanes_in_use") *value = kk::spiluk_lanes(h);
   else if (k == "stage_entries_per_lane") *value = kk::kStage;
   else if (k == "symbolic_fill_us") *value = h->fill_us;
   else if (k == "symbolic_other_us") *value = h->levels_us;
-  else if (k == "plan_bytes")   // HBM the handle keeps: the rows grouped by level and the level offsets
-    *value = h->d_grouped ? (int64_t)sizeof(int32_t) * h->nrows + (int64_t)sizeof(int64_t) * (h->num_levels() + 1) : 0;
+  else if (k == "plan_bytes")   // the rows grouped by level and the level offsets; an empty matrix counts its one offset, as it always has
+    *value = h->symbolic_complete ? (int64_t)sizeof(int32_t) * h->nrows + (int64_t)sizeof(int64_t) * (h->sched.num_levels() + 1) : 0;
   else return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spiluk_get: unknown key '%s'", key);
   return KKAMD_OK;
 }

@@ -14,15 +14,16 @@
 //      as row_map).
 // level_list is a function of the graph alone, the other two arrays are functions of level_list: the order of the atomics changes
 // nothing.  One host synchronisation per level (the queue's tail); at most num_rows levels.
+// The analysis fills a kk::LevelSchedule (kk_levels.h) through analyse_levels, which ILU(k) calls too (kk_spiluk.hip); the launches of one
+// solve are built from it and the knobs.
 //
 // Solve phase.  One launch per level: a group of LPR lanes owns one row of the level's list, strides over its entries, skips the
 // diagonal position, reduces with kk::group_sum (fixed order: the same bits on every run) and its first lane writes x[row].  Runs of
 // consecutive narrow levels may be chained into one single-workgroup launch with __syncthreads() between the levels.
 // No work-item ever waits on another workgroup: every dependency between workgroups is a kernel boundary on the stream.
-#include "kk_common.h"
+#include "kk_levels.h"
 #include <climits>
 #include <new>
-#include <vector>
 
 namespace kk {
 
@@ -91,6 +92,98 @@ __global__ __launch_bounds__(kBlock) void sptrsv_peel_kernel(int32_t* queue, int
   }
 }
 
+template <class OffT>
+static int analyse_levels_typed(LevelSchedule* s, int64_t n, int lower, const OffT* rm, const int32_t* ent, int offset_type, hipStream_t st,
+                                DevBuf* level_b, DevBuf* diag_b) {
+  DevBuf grouped_b, off_b, indeg_b, ctr_b, trm_b, tent_b;
+  KK_HIP(level_b->alloc(sizeof(int32_t) * (size_t)n));
+  KK_HIP(grouped_b.alloc(sizeof(int32_t) * (size_t)n));
+  KK_HIP(diag_b->alloc(sizeof(int32_t) * (size_t)n));
+  KK_HIP(indeg_b.alloc(sizeof(int32_t) * (size_t)n));
+  KK_HIP(ctr_b.alloc(sizeof(unsigned long long) * 3));
+  int32_t *level_list = level_b->as<int32_t>(), *queue = grouped_b.as<int32_t>(), *indeg = indeg_b.as<int32_t>(), *diagpos = diag_b->as<int32_t>();
+  unsigned long long* ctr = ctr_b.as<unsigned long long>();
+  KK_HIP(hipMemsetAsync(ctr, 0, 16, st));
+  KK_HIP(hipMemsetAsync(ctr + 2, 0xFF, 8, st));
+  KK_LAUNCH((sptrsv_validate_kernel<OffT>), (unsigned)ceil_div(n * kSymLanes, kBlock), kBlock, 0, st, n, lower, rm, ent, diagpos, indeg,
+            level_list, queue, ctr);
+  KK_LAUNCH_CHECK();
+  unsigned long long hc[3] = {0, 0, 0};
+  OffT h_nnz = 0;
+  KK_HIP(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, st));
+  KK_HIP(hipMemcpyAsync(&h_nnz, rm + n, sizeof(OffT), hipMemcpyDeviceToHost, st));
+  KK_HIP(hipStreamSynchronize(st));
+  if (hc[2] != kNoError) {
+    static const char* const what[] = {"its row_map offsets are not ascending (or it has more than 2^31 - 1 entries)",
+                                       "a column is outside [0, num_rows)", "", "it has no diagonal entry", "it has more than one diagonal entry"};
+    const long long row = (long long)(hc[2] >> 3);
+    const int kind = (int)(hc[2] & 7);
+    if (kind == kErrSide)
+      return fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_symbolic: row %lld: an entry lies %s the diagonal of a%s triangular matrix", row,
+                  lower ? "above" : "below", lower ? " lower" : "n upper");
+    return fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_symbolic: row %lld: %s", row, what[kind]);
+  }
+  const int64_t nnz = (int64_t)h_nnz;
+  int64_t head = 0, tail = (int64_t)hc[0];
+  if (tail == 0) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: no row without off-diagonal entries (internal error)");
+  if (tail < n) {
+    // row j of the transpose: the rows that read x[j]
+    KK_HIP(trm_b.alloc(sizeof(OffT) * (size_t)(n + 1)));
+    KK_HIP(tent_b.alloc(sizeof(int32_t) * (size_t)nnz));
+    const int rc = kkamd_transpose(n, n, nnz, rm, ent, nullptr, offset_type, KKAMD_F64, trm_b.p, tent_b.as<int32_t>(), nullptr,
+                                   reinterpret_cast<kkamd_stream_t>(st));
+    if (rc) return rc;
+  }
+  const OffT* t_rm = trm_b.as<OffT>();
+  const int32_t* t_ent = tent_b.as<int32_t>();
+  std::vector<int64_t> level_off(1, 0), level_entries;
+  unsigned long long entries_before = 0;
+  for (int64_t lvl = 1;; ++lvl) {                            // at most n levels: every level holds at least one row
+    level_off.push_back(tail);
+    level_entries.push_back((int64_t)(hc[1] - entries_before));
+    entries_before = hc[1];
+    if (tail >= n) break;
+    if (lvl >= n) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: more levels than rows (internal error)");
+    const int64_t cnt = tail - head;
+    KK_LAUNCH((sptrsv_peel_kernel<OffT>), (unsigned)ceil_div(cnt * kSymLanes, kBlock), kBlock, 0, st, queue, head, cnt, t_rm, t_ent, rm, indeg, level_list, (int32_t)(lvl + 1), ctr);
+    KK_LAUNCH_CHECK();
+    KK_HIP(hipMemcpyAsync(hc, ctr, 16, hipMemcpyDeviceToHost, st));
+    KK_HIP(hipStreamSynchronize(st));
+    if ((int64_t)hc[0] <= tail) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: level %lld released no row (internal error)", (long long)lvl);
+    head = tail;
+    tail = (int64_t)hc[0];
+  }
+  trm_b.reset(); tent_b.reset(); indeg_b.reset(); ctr_b.reset();
+  const int64_t L = (int64_t)level_off.size() - 1;
+  KK_HIP(off_b.alloc(sizeof(int64_t) * (size_t)(L + 1)));
+  KK_HIP(hipMemcpyAsync(off_b.p, level_off.data(), sizeof(int64_t) * (size_t)(L + 1), hipMemcpyHostToDevice, st));
+  KK_HIP(hipStreamSynchronize(st));
+  // ascending row order inside every level
+  const int rc = kkamd_sort_crs(L, off_b.p, queue, nullptr, KKAMD_I64, KKAMD_F64, reinterpret_cast<kkamd_stream_t>(st));
+  if (rc) return rc;
+  KK_HIP(hipStreamSynchronize(st));
+  s->d_grouped   = (int32_t*)grouped_b.release();
+  s->d_level_off = (int64_t*)off_b.release();
+  s->level_off.swap(level_off);
+  s->level_entries.swap(level_entries);
+  for (int64_t l = 0; l < L; ++l) {
+    const int64_t w = s->level_off[l + 1] - s->level_off[l];
+    if (w > s->max_level_rows) s->max_level_rows = w;
+  }
+  return KKAMD_OK;
+}
+
+int analyse_levels(LevelSchedule* s, int64_t n, int lower, const void* row_map, const int32_t* entries, int offset_type, hipStream_t st,
+                   DevBuf* level_list, DevBuf* diagpos) {
+  if (n == 0) {
+    KK_HIP(hipStreamSynchronize(st));
+    s->level_off.assign(1, 0);
+    return KKAMD_OK;
+  }
+  return offset_type == KKAMD_I64 ? analyse_levels_typed<int64_t>(s, n, lower, (const int64_t*)row_map, entries, offset_type, st, level_list, diagpos)
+                                  : analyse_levels_typed<int32_t>(s, n, lower, (const int32_t*)row_map, entries, offset_type, st, level_list, diagpos);
+}
+
 // One row per group of lpr lanes (a power of two, 1..64).  x of the row's off-diagonal columns was written by an earlier launch, or
 // by this workgroup before its last barrier.  b may be x: b[row] is read by the lane that writes x[row].  Neither pointer is
 // const / __restrict__, so x is read with ordinary vector loads.
@@ -135,171 +228,47 @@ __global__ __launch_bounds__(kBlock) void sptrsv_chain_kernel(const int32_t* __r
   }
 }
 
-struct SptrsvLaunch {
-  int first, nlev;      // levels covered
-  int lpr, chain;
-};
-
 }  // namespace kk
 
 struct kkamd_sptrsv_handle {
   int algorithm = 0, lower = 1;
   int64_t nrows = 0;
-  int lanes_per_row = 0, chain_rows = 64, chain_levels = 1024;
   bool symbolic_complete = false;
-  int32_t *d_level_list = nullptr, *d_grouped = nullptr, *d_diagpos = nullptr;
-  int64_t* d_level_off = nullptr;
-  std::vector<int64_t> level_off, level_entries;        // host: num_levels + 1 offsets into the grouped list, entries per level
-  std::vector<kk::SptrsvLaunch> plan;                   // the launches of one solve
-  int64_t max_level_rows = 0, chain_launches = 0, chained_levels = 0;
+  kk::LevelSchedule sched;
+  int32_t *d_level_list = nullptr, *d_diagpos = nullptr;
 
-  void free_device() {
+  void clear_symbolic() {
+    symbolic_complete = false;
+    sched.clear();
     if (d_level_list) (void)hipFree(d_level_list);
-    if (d_grouped) (void)hipFree(d_grouped);
     if (d_diagpos) (void)hipFree(d_diagpos);
-    if (d_level_off) (void)hipFree(d_level_off);
-    d_level_list = d_grouped = d_diagpos = nullptr;
-    d_level_off = nullptr;
+    d_level_list = d_diagpos = nullptr;
   }
-  int64_t num_levels() const { return level_off.empty() ? 0 : (int64_t)level_off.size() - 1; }
 };
 
 namespace kk {
 
-static int log2i(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
-
-// the smallest power of two that covers the mean row length (diagonal included), 1..64: one pass over an average row.  On the lower
+// The launches of one solve.  Lanes per row: what covers the mean row length (diagonal included) of the launch's levels.  On the lower
 // triangle of the 27-point lattice (13.9 entries per row) 16 lanes measured 5 % faster than 8
-static int lanes_for(const kkamd_sptrsv_handle* h, int64_t entries, int64_t rows) {
-  if (h->algorithm == KKAMD_SPTRSV_SEQLVLSCHD_RP) return 1;
-  if (h->lanes_per_row) return h->lanes_per_row;
-  const int64_t mean = rows > 0 ? ceil_div(entries, rows) : 1;
-  int lpr = 1;
-  while (lpr < kWave && lpr < mean) lpr *= 2;
-  return lpr;
-}
-
-// the launches of one solve from the level sizes and the knobs
-static void build_plan(kkamd_sptrsv_handle* h) {
-  h->plan.clear();
-  h->chain_launches = h->chained_levels = 0;
-  const int64_t L = h->num_levels();
-  const bool chaining = h->algorithm == KKAMD_SPTRSV_SEQLVLSCHD_TP1CHAIN && h->chain_rows > 0;
-  int64_t l = 0;
-  while (l < L) {
-    int64_t run = 0;
-    if (chaining)
-      while (l + run < L && h->level_off[l + run + 1] - h->level_off[l + run] <= h->chain_rows) ++run;
-    if (run < 2) {
-      h->plan.push_back({(int)l, 1, lanes_for(h, h->level_entries[l], h->level_off[l + 1] - h->level_off[l]), 0});
-      ++l;
-      continue;
-    }
-    for (int64_t p = 0; p < run; p += h->chain_levels) {
-      const int64_t nl = run - p < h->chain_levels ? run - p : h->chain_levels;
-      int64_t entries = 0;
-      for (int64_t q = l + p; q < l + p + nl; ++q) entries += h->level_entries[q];
-      h->plan.push_back({(int)(l + p), (int)nl, lanes_for(h, entries, h->level_off[l + p + nl] - h->level_off[l + p]), 1});
-      h->chain_launches += 1;
-      h->chained_levels += nl;
-    }
-    l += run;
-  }
-}
-
-template <class OffT>
-static int sptrsv_symbolic_typed(kkamd_sptrsv_handle* h, int64_t n, const OffT* rm, const int32_t* ent, int offset_type, hipStream_t st) {
-  DevBuf level_b, grouped_b, diag_b, off_b, indeg_b, ctr_b, trm_b, tent_b;
-  KK_HIP(level_b.alloc(sizeof(int32_t) * (size_t)n));
-  KK_HIP(grouped_b.alloc(sizeof(int32_t) * (size_t)n));
-  KK_HIP(diag_b.alloc(sizeof(int32_t) * (size_t)n));
-  KK_HIP(indeg_b.alloc(sizeof(int32_t) * (size_t)n));
-  KK_HIP(ctr_b.alloc(sizeof(unsigned long long) * 3));
-  int32_t *level_list = level_b.as<int32_t>(), *queue = grouped_b.as<int32_t>(), *indeg = indeg_b.as<int32_t>(), *diagpos = diag_b.as<int32_t>();
-  const int lower = h->lower;
-  unsigned long long* ctr = ctr_b.as<unsigned long long>();
-  KK_HIP(hipMemsetAsync(ctr, 0, 16, st));
-  KK_HIP(hipMemsetAsync(ctr + 2, 0xFF, 8, st));
-  KK_LAUNCH((sptrsv_validate_kernel<OffT>), (unsigned)ceil_div(n * kSymLanes, kBlock), kBlock, 0, st, n, lower, rm, ent, diagpos, indeg,
-            level_list, queue, ctr);
-  KK_LAUNCH_CHECK();
-  unsigned long long hc[3] = {0, 0, 0};
-  OffT h_nnz = 0;
-  KK_HIP(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, st));
-  KK_HIP(hipMemcpyAsync(&h_nnz, rm + n, sizeof(OffT), hipMemcpyDeviceToHost, st));
-  KK_HIP(hipStreamSynchronize(st));
-  if (hc[2] != kNoError) {
-    static const char* const what[] = {"its row_map offsets are not ascending (or it has more than 2^31 - 1 entries)",
-                                       "a column is outside [0, num_rows)", "", "it has no diagonal entry", "it has more than one diagonal entry"};
-    const long long row = (long long)(hc[2] >> 3);
-    const int kind = (int)(hc[2] & 7);
-    if (kind == kErrSide)
-      return fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_symbolic: row %lld: an entry lies %s the diagonal of a%s triangular matrix", row,
-                  h->lower ? "above" : "below", h->lower ? " lower" : "n upper");
-    return fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_symbolic: row %lld: %s", row, what[kind]);
-  }
-  const int64_t nnz = (int64_t)h_nnz;
-  int64_t head = 0, tail = (int64_t)hc[0];
-  if (tail == 0) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: no row without off-diagonal entries (internal error)");
-  if (tail < n) {
-    // row j of the transpose: the rows that read x[j]
-    KK_HIP(trm_b.alloc(sizeof(OffT) * (size_t)(n + 1)));
-    KK_HIP(tent_b.alloc(sizeof(int32_t) * (size_t)nnz));
-    const int rc = kkamd_transpose(n, n, nnz, rm, ent, nullptr, offset_type, KKAMD_F64, trm_b.p, tent_b.as<int32_t>(), nullptr,
-                                   reinterpret_cast<kkamd_stream_t>(st));
-    if (rc) return rc;
-  }
-  const OffT* t_rm = trm_b.as<OffT>();
-  const int32_t* t_ent = tent_b.as<int32_t>();
-  std::vector<int64_t> level_off(1, 0), level_entries;
-  unsigned long long entries_before = 0;
-  for (int64_t lvl = 1;; ++lvl) {                            // at most n levels: every level holds at least one row
-    level_off.push_back(tail);
-    level_entries.push_back((int64_t)(hc[1] - entries_before));
-    entries_before = hc[1];
-    if (tail >= n) break;
-    if (lvl >= n) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: more levels than rows (internal error)");
-    const int64_t cnt = tail - head;
-    KK_LAUNCH((sptrsv_peel_kernel<OffT>), (unsigned)ceil_div(cnt * kSymLanes, kBlock), kBlock, 0, st, queue, head, cnt, t_rm, t_ent, rm, indeg, level_list, (int32_t)(lvl + 1), ctr);
-    KK_LAUNCH_CHECK();
-    KK_HIP(hipMemcpyAsync(hc, ctr, 16, hipMemcpyDeviceToHost, st));
-    KK_HIP(hipStreamSynchronize(st));
-    if ((int64_t)hc[0] <= tail) return fail(KKAMD_ERR_STATE, "kkamd_sptrsv_symbolic: level %lld released no row (internal error)", (long long)lvl);
-    head = tail;
-    tail = (int64_t)hc[0];
-  }
-  trm_b.reset(); tent_b.reset(); indeg_b.reset(); ctr_b.reset();
-  const int64_t L = (int64_t)level_off.size() - 1;
-  KK_HIP(off_b.alloc(sizeof(int64_t) * (size_t)(L + 1)));
-  KK_HIP(hipMemcpyAsync(off_b.p, level_off.data(), sizeof(int64_t) * (size_t)(L + 1), hipMemcpyHostToDevice, st));
-  KK_HIP(hipStreamSynchronize(st));
-  // ascending row order inside every level
-  const int rc = kkamd_sort_crs(L, off_b.p, queue, nullptr, KKAMD_I64, KKAMD_F64, reinterpret_cast<kkamd_stream_t>(st));
-  if (rc) return rc;
-  KK_HIP(hipStreamSynchronize(st));
-  h->d_level_list = (int32_t*)level_b.release();
-  h->d_grouped    = (int32_t*)grouped_b.release();
-  h->d_diagpos    = (int32_t*)diag_b.release();
-  h->d_level_off  = (int64_t*)off_b.release();
-  h->level_off.swap(level_off);
-  h->level_entries.swap(level_entries);
-  for (int64_t l = 0; l < L; ++l) {
-    const int64_t w = h->level_off[l + 1] - h->level_off[l];
-    if (w > h->max_level_rows) h->max_level_rows = w;
-  }
-  return KKAMD_OK;
+static void sptrsv_build_plan(kkamd_sptrsv_handle* h) {
+  build_plan(&h->sched, h->algorithm == KKAMD_SPTRSV_SEQLVLSCHD_TP1CHAIN && h->sched.chain_rows > 0, [h](int64_t entries, int64_t rows) {
+    if (h->algorithm == KKAMD_SPTRSV_SEQLVLSCHD_RP) return 1;
+    if (h->sched.lanes_per_row) return h->sched.lanes_per_row;
+    return pow2_covering(rows > 0 ? ceil_div(entries, rows) : 1);
+  });
 }
 
 template <class OffT, class VT>
 static int sptrsv_solve_typed(const kkamd_sptrsv_handle* h, const OffT* rm, const int32_t* ent, const VT* val, const VT* b, VT* x, hipStream_t st) {
-  for (const SptrsvLaunch& q : h->plan) {
+  const LevelSchedule& s = h->sched;
+  for (const LevelLaunch& q : s.plan) {
     const int sh = log2i(q.lpr);
     if (q.chain) {
-      KK_LAUNCH((sptrsv_chain_kernel<OffT, VT>), 1u, kBlock, 0, st, (const int32_t*)h->d_grouped, (const int64_t*)h->d_level_off, q.first, q.nlev, q.lpr,
+      KK_LAUNCH((sptrsv_chain_kernel<OffT, VT>), 1u, kBlock, 0, st, (const int32_t*)s.d_grouped, (const int64_t*)s.d_level_off, q.first, q.nlev, q.lpr,
                 sh, rm, ent, val, (const int32_t*)h->d_diagpos, b, x);
     } else {
-      const int64_t beg = h->level_off[q.first], cnt = h->level_off[q.first + 1] - beg;
-      KK_LAUNCH((sptrsv_level_kernel<OffT, VT>), (unsigned)ceil_div(cnt * q.lpr, kBlock), kBlock, 0, st, (const int32_t*)(h->d_grouped + beg), cnt, q.lpr,
+      const int64_t beg = s.level_off[q.first], cnt = s.level_off[q.first + 1] - beg;
+      KK_LAUNCH((sptrsv_level_kernel<OffT, VT>), (unsigned)ceil_div(cnt * q.lpr, kBlock), kBlock, 0, st, (const int32_t*)(s.d_grouped + beg), cnt, q.lpr,
                 sh, rm, ent, val, (const int32_t*)h->d_diagpos, b, x);
     }
   }
@@ -331,7 +300,7 @@ int kkamd_sptrsv_create(kkamd_sptrsv_handle_t** handle, int algorithm, int64_t n
 
 int kkamd_sptrsv_destroy(kkamd_sptrsv_handle_t* h) {
   if (!h) return KKAMD_OK;
-  h->free_device();
+  h->clear_symbolic();
   delete h;
   return KKAMD_OK;
 }
@@ -345,21 +314,13 @@ int kkamd_sptrsv_symbolic(kkamd_sptrsv_handle_t* h, int64_t num_rows, const void
   if (num_rows > 0 && (!d_row_map || !d_entries)) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_symbolic: null pointer");
   kk::TraceRange range("KokkosSparse::sptrsv_symbolic[TPL_KKAMD]");
   hipStream_t st = kk::to_hip(stream);
-  // a repeated call analyses again
-  h->symbolic_complete = false;
-  h->free_device();
-  h->level_off.clear(); h->level_entries.clear(); h->plan.clear();
-  h->max_level_rows = h->chain_launches = h->chained_levels = 0;
-  int rc = KKAMD_OK;
-  if (num_rows > 0) {
-    rc = offset_type == KKAMD_I64 ? kk::sptrsv_symbolic_typed<int64_t>(h, num_rows, (const int64_t*)d_row_map, d_entries, offset_type, st)
-                                  : kk::sptrsv_symbolic_typed<int32_t>(h, num_rows, (const int32_t*)d_row_map, d_entries, offset_type, st);
-  } else {
-    h->level_off.assign(1, 0);
-    KK_HIP(hipStreamSynchronize(st));
-  }
-  if (rc) { h->level_off.clear(); h->level_entries.clear(); return rc; }
-  kk::build_plan(h);
+  h->clear_symbolic();                                       // a repeated call analyses again
+  kk::DevBuf level_list, diagpos;
+  const int rc = kk::analyse_levels(&h->sched, num_rows, h->lower, d_row_map, d_entries, offset_type, st, &level_list, &diagpos);
+  if (rc) return rc;
+  h->d_level_list = (int32_t*)level_list.release();
+  h->d_diagpos    = (int32_t*)diagpos.release();
+  kk::sptrsv_build_plan(h);
   h->symbolic_complete = true;
   return KKAMD_OK;
 }
@@ -387,40 +348,22 @@ int kkamd_sptrsv_solve(kkamd_sptrsv_handle_t* h, int64_t num_rows, const void* d
 
 int kkamd_sptrsv_set(kkamd_sptrsv_handle_t* h, const char* key, int value) {
   if (!h || !key) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_set: null argument");
-  const std::string k(key);
-  if (k == "lanes_per_row") {
-    if (value < 0 || value > kk::kWave || (value & (value - 1))) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_set: lanes_per_row %d is not 0 or a power of two up to 64", value);
-    h->lanes_per_row = value;
-  } else if (k == "chain_rows") {
-    if (value < 0) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_set: chain_rows %d is negative", value);
-    h->chain_rows = value;
-  } else if (k == "chain_levels") {
-    if (value < 1) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_set: chain_levels %d is below 1", value);
-    h->chain_levels = value;
-  } else {
-    return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_set: unknown key '%s'", key);
-  }
-  if (h->symbolic_complete) kk::build_plan(h);
+  const int rc = kk::set_knob(&h->sched, "kkamd_sptrsv_set", key, value);
+  if (rc) return rc;
+  if (h->symbolic_complete) kk::sptrsv_build_plan(h);
   return KKAMD_OK;
 }
 
 int kkamd_sptrsv_get(const kkamd_sptrsv_handle_t* h, const char* key, int64_t* value) {
   if (!h || !key || !value) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_get: null argument");
   const std::string k(key);
-  if (k == "num_levels") *value = h->num_levels();
-  else if (k == "symbolic_complete") *value = h->symbolic_complete ? 1 : 0;
+  if (kk::get_common(h->sched, k, value)) return KKAMD_OK;
+  if (k == "symbolic_complete") *value = h->symbolic_complete ? 1 : 0;
   else if (k == "lower_tri") *value = h->lower;
   else if (k == "algorithm") *value = h->algorithm;
   else if (k == "num_rows") *value = h->nrows;
-  else if (k == "max_level_rows") *value = h->max_level_rows;
-  else if (k == "launches") *value = (int64_t)h->plan.size();
-  else if (k == "chain_launches") *value = h->chain_launches;
-  else if (k == "chained_levels") *value = h->chained_levels;
-  else if (k == "lanes_per_row") *value = h->lanes_per_row;
-  else if (k == "chain_rows") *value = h->chain_rows;
-  else if (k == "chain_levels") *value = h->chain_levels;
   else if (k == "plan_bytes")
-    *value = h->d_level_list ? (int64_t)(3 * sizeof(int32_t)) * h->nrows + (int64_t)sizeof(int64_t) * (h->num_levels() + 1) : 0;
+    *value = h->d_level_list ? (int64_t)(3 * sizeof(int32_t)) * h->nrows + (int64_t)sizeof(int64_t) * (h->sched.num_levels() + 1) : 0;
   else return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_get: unknown key '%s'", key);
   return KKAMD_OK;
 }
@@ -431,16 +374,16 @@ int kkamd_sptrsv_export(const kkamd_sptrsv_handle_t* h, const char* what, void* 
   const std::string k(what);
   const bool per_level = k == "nodes_per_level";
   if (!per_level && k != "level_list" && k != "nodes_grouped_by_level") return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_export: unknown array '%s'", what);
-  const int64_t need = per_level ? h->num_levels() : h->nrows;
+  const int64_t need = per_level ? h->sched.num_levels() : h->nrows;
   if (count != need) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_export: '%s' has %lld entries, not %lld", what, (long long)need, (long long)count);
   if (need == 0) return KKAMD_OK;
   if (!h_out) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_sptrsv_export: null output");
   int32_t* out = (int32_t*)h_out;
   if (per_level) {
-    for (int64_t l = 0; l < need; ++l) out[l] = (int32_t)(h->level_off[l + 1] - h->level_off[l]);
+    for (int64_t l = 0; l < need; ++l) out[l] = (int32_t)(h->sched.level_off[l + 1] - h->sched.level_off[l]);
     return KKAMD_OK;
   }
-  KK_HIP(hipMemcpy(out, k == "level_list" ? h->d_level_list : h->d_grouped, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost));
+  KK_HIP(hipMemcpy(out, k == "level_list" ? h->d_level_list : h->sched.d_grouped, sizeof(int32_t) * (size_t)need, hipMemcpyDeviceToHost));
   return KKAMD_OK;
 }
 

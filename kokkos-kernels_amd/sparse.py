@@ -377,41 +377,41 @@ class KokkosKernelsHandle:
 _SPTRSV_ALGOS = {"SEQLVLSCHD_RP": 0, "SEQLVLSCHD_TP1": 1, "SEQLVLSCHD_TP1CHAIN": 2, "SPTRSV_CUSPARSE": 3}
 
 
-class _SptrsvHandle:
-    """KokkosSparse::Experimental::SPTRSVHandle as far as the level-scheduled solve uses it (sparse/src/KokkosSparse_sptrsv_handle.hpp):
-    algorithm, size and triangle, the level sets of the symbolic phase, and this library's knobs."""
+class _LevelHandle:
+    """What the handles of the level-scheduled routines share: the kkamd_<prefix>_create / set / get / export / destroy calls."""
+    PER_LEVEL = {}   # export name -> its entries beyond num_levels; every other array has num_rows entries
 
-    def __init__(self, backend, algo, nrows, lower_tri):
-        self.backend, self.algo = backend, algo
+    def __init__(self, backend, algo, prefix, *create_args):
+        self.backend, self.algo, self.prefix = backend, algo, prefix
         self.h = C.c_void_p()
-        check(backend.lib, backend.lib.kkamd_sptrsv_create(C.byref(self.h), _SPTRSV_ALGOS[algo], int(nrows), 1 if lower_tri else 0))
+        check(backend.lib, self._fn("create")(C.byref(self.h), *create_args))
+
+    def _fn(self, name): return getattr(self.backend.lib, "kkamd_%s_%s" % (self.prefix, name))
 
     def set(self, key, value):
-        """"lanes_per_row", "chain_rows", "chain_levels" (kkamd_sptrsv_set)"""
-        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_set(self.h, key.encode(), int(value)))
+        """"lanes_per_row", "chain_rows", "chain_levels" (kkamd_sptrsv_set, kkamd_spiluk_set)"""
+        check(self.backend.lib, self._fn("set")(self.h, key.encode(), int(value)))
 
     def get(self, key):
         v = C.c_int64()
-        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_get(self.h, key.encode(), C.byref(v)))
+        check(self.backend.lib, self._fn("get")(self.h, key.encode(), C.byref(v)))
         return int(v.value)
 
     def export(self, what):
-        """"level_list", "nodes_per_level" or "nodes_grouped_by_level" as a host int32 array"""
-        n = self.get("num_levels") if what == "nodes_per_level" else self.get("num_rows")
+        """one of the handle's arrays (its class names them) as a host int32 array"""
+        n = self.get("num_levels") + self.PER_LEVEL[what] if what in self.PER_LEVEL else self.get("num_rows")
         out = np.zeros(n, dtype=np.int32)
-        check(self.backend.lib, self.backend.lib.kkamd_sptrsv_export(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), n))
+        check(self.backend.lib, self._fn("export")(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), n))
         return out
 
     def get_algorithm(self): return self.algo
     def get_nrows(self): return self.get("num_rows")
-    def is_lower_tri(self): return bool(self.get("lower_tri"))
-    def is_upper_tri(self): return not self.is_lower_tri()
     def get_num_levels(self): return self.get("num_levels")
     def is_symbolic_complete(self): return bool(self.get("symbolic_complete"))
 
     def destroy(self):
         if self.h:
-            self.backend.lib.kkamd_sptrsv_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -421,17 +421,30 @@ class _SptrsvHandle:
             pass
 
 
-def _sptrsv_handle(kh, who):
-    th = kh.get_sptrsv_handle() if kh is not None else None
-    if th is None:
-        raise ValueError("KokkosSparse::%s: the given KernelHandle does not have an SPTRSV handle associated with it." % who)
-    return th
+def _sub_handle(kh, getter, name, who):
+    sub = getattr(kh, getter)() if kh is not None else None
+    if sub is None:
+        raise ValueError("KokkosSparse::%s: the given KernelHandle does not have an %s handle associated with it." % (who, name))
+    return sub
+
+
+class _SptrsvHandle(_LevelHandle):
+    """KokkosSparse::Experimental::SPTRSVHandle as far as the level-scheduled solve uses it (sparse/src/KokkosSparse_sptrsv_handle.hpp):
+    algorithm, size and triangle, the level sets of the symbolic phase, and this library's knobs.
+    export: "level_list", "nodes_per_level" or "nodes_grouped_by_level"."""
+    PER_LEVEL = {"nodes_per_level": 0}
+
+    def __init__(self, backend, algo, nrows, lower_tri):
+        super().__init__(backend, algo, "sptrsv", _SPTRSV_ALGOS[algo], int(nrows), 1 if lower_tri else 0)
+
+    def is_lower_tri(self): return bool(self.get("lower_tri"))
+    def is_upper_tri(self): return not self.is_lower_tri()
 
 
 def sptrsv_symbolic(kh, row_map, entries):
     """KokkosSparse::sptrsv_symbolic(handle, rowmap, entries) (sparse/src/KokkosSparse_sptrsv.hpp:54-122): validates the triangle and
     builds the level sets on the device.  May be repeated."""
-    th = _sptrsv_handle(kh, "sptrsv_symbolic")
+    th = _sub_handle(kh, "get_sptrsv_handle", "SPTRSV", "sptrsv_symbolic")
     be, lib = th.backend, th.backend.lib
     check(lib, lib.kkamd_sptrsv_symbolic(th.h, int(row_map.shape[0]) - 1, be.ptr(row_map), be.ptr(entries), _offset_type(row_map), be.stream()))
 
@@ -439,7 +452,7 @@ def sptrsv_symbolic(kh, row_map, entries):
 def sptrsv_solve(kh, row_map, entries, values, b, x):
     """KokkosSparse::sptrsv_solve(handle, rowmap, entries, values, b, x) (sparse/src/KokkosSparse_sptrsv.hpp:268-411): x := A^-1 b on the
     backend's current stream; b may be x.  b and x are rank 1 and contiguous."""
-    th = _sptrsv_handle(kh, "sptrsv_solve")
+    th = _sub_handle(kh, "get_sptrsv_handle", "SPTRSV", "sptrsv_solve")
     be, lib = th.backend, th.backend.lib
     if len(b.shape) != 1 or len(x.shape) != 1:
         raise RuntimeError("KokkosSparse::sptrsv_solve: b and x must have rank 1")
@@ -463,62 +476,24 @@ def sptrsv_solve(kh, row_map, entries, values, b, x):
 _SPILUK_ALGOS = {"SEQLVLSCHD_TP1": 0}
 
 
-class _SpilukHandle:
+class _SpilukHandle(_LevelHandle):
     """KokkosSparse::Experimental::SPILUKHandle as far as the level-scheduled factorisation uses it
-    (sparse/src/KokkosSparse_spiluk_handle.hpp): algorithm, size, nnzL and nnzU, the level sets of L, and this library's knobs."""
+    (sparse/src/KokkosSparse_spiluk_handle.hpp): algorithm, size, nnzL and nnzU, the level sets of L, and this library's knobs.
+    export: "level_list" (1-based), "level_ptr" (num_levels + 1) or "level_idx"."""
+    PER_LEVEL = {"level_ptr": 1}
 
     def __init__(self, backend, algo, nrows, nnzL, nnzU):
-        self.backend, self.algo = backend, algo
-        self.h = C.c_void_p()
-        check(backend.lib, backend.lib.kkamd_spiluk_create(C.byref(self.h), _SPILUK_ALGOS[algo], int(nrows), int(nnzL), int(nnzU)))
+        super().__init__(backend, algo, "spiluk", _SPILUK_ALGOS[algo], int(nrows), int(nnzL), int(nnzU))
 
-    def set(self, key, value):
-        """"lanes_per_row", "chain_rows", "chain_levels" (kkamd_spiluk_set)"""
-        check(self.backend.lib, self.backend.lib.kkamd_spiluk_set(self.h, key.encode(), int(value)))
-
-    def get(self, key):
-        v = C.c_int64()
-        check(self.backend.lib, self.backend.lib.kkamd_spiluk_get(self.h, key.encode(), C.byref(v)))
-        return int(v.value)
-
-    def export(self, what):
-        """"level_list" (1-based), "level_ptr" (num_levels + 1) or "level_idx" as a host int32 array"""
-        n = self.get("num_levels") + 1 if what == "level_ptr" else self.get("num_rows")
-        out = np.zeros(n, dtype=np.int32)
-        check(self.backend.lib, self.backend.lib.kkamd_spiluk_export(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), n))
-        return out
-
-    def get_algorithm(self): return self.algo
-    def get_nrows(self): return self.get("num_rows")
     def get_nnzL(self): return self.get("nnzL")
     def get_nnzU(self): return self.get("nnzU")
-    def get_num_levels(self): return self.get("num_levels")
-    def is_symbolic_complete(self): return bool(self.get("symbolic_complete"))
-
-    def destroy(self):
-        if self.h:
-            self.backend.lib.kkamd_spiluk_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-def _spiluk_handle(kh, who):
-    ih = kh.get_spiluk_handle() if kh is not None else None
-    if ih is None:
-        raise ValueError("KokkosSparse::%s: the given KernelHandle does not have an SPILUK handle associated with it." % who)
-    return ih
 
 
 def spiluk_symbolic(kh, fill_lev, A_row_map, A_entries, L_row_map, L_entries, U_row_map, U_entries):
     """KokkosSparse::spiluk_symbolic(handle, fill_lev, A_rowmap, A_entries, L_rowmap, L_entries, U_rowmap, U_entries)
     (sparse/src/KokkosSparse_spiluk.hpp:42-197): writes the graphs of L and U for level of fill fill_lev and records nnzL, nnzU and the
     level sets of L in the handle.  The extents of L_entries / U_entries are the capacities.  May be repeated."""
-    ih = _spiluk_handle(kh, "spiluk_symbolic")
+    ih = _sub_handle(kh, "get_spiluk_handle", "SPILUK", "spiluk_symbolic")
     be, lib = ih.backend, ih.backend.lib
     n = int(A_row_map.shape[0]) - 1
     if L_row_map.shape[0] != n + 1 or U_row_map.shape[0] != n + 1:
@@ -534,7 +509,7 @@ def spiluk_numeric(kh, fill_lev, A_row_map, A_entries, A_values, L_row_map, L_en
     """KokkosSparse::spiluk_numeric(handle, fill_lev, A_rowmap, A_entries, A_values, L_rowmap, L_entries, L_values, U_rowmap, U_entries,
     U_values) (sparse/src/KokkosSparse_spiluk.hpp:200-415): the ILU(k) factors of A on the analysed pattern, on the backend's current
     stream.  New values of A need no second symbolic call."""
-    ih = _spiluk_handle(kh, "spiluk_numeric")
+    ih = _sub_handle(kh, "get_spiluk_handle", "SPILUK", "spiluk_numeric")
     be, lib = ih.backend, ih.backend.lib
     n = int(A_row_map.shape[0]) - 1
     if _np_dtype(L_values) != _np_dtype(A_values) or _np_dtype(U_values) != _np_dtype(A_values):

@@ -2,6 +2,7 @@
 # sets from (kk_sptrsv.hip), for tests/test_emu_spiluk.py.  Makefile itself stays as it is; its objects are shared.
 include Makefile
 kk_spiluk.emu.o: $(CSRC)/kk_spiluk_fill.h
+kk_sptrsv.emu.o kk_spiluk.emu.o: $(CSRC)/kk_levels.h
 libkkamd_emu_spiluk.so: $(OBJS) kk_sptrsv.emu.o kk_spiluk.emu.o
 	$(CXX) -shared -o $@ $(OBJS) kk_sptrsv.emu.o kk_spiluk.emu.o
 # the host side of the symbolic phase alone, under the host sanitizers

@@ -137,6 +137,29 @@ def test_rounded_values_meet_the_identity_bound():
             f.close()
 
 
+def test_empty_matrix():
+    """0 rows: an analysis with no level and no launch, whose plan_bytes counts the one level offset; numeric returns"""
+    kk, be = backend()
+    kh = kk.KokkosKernelsHandle(be)
+    kh.create_spiluk_handle("SEQLVLSCHD_TP1", 0, 0, 0)
+    ih = kh.get_spiluk_handle()
+    rm = lambda: be.from_numpy(np.zeros(1, dtype=np.int32))
+    ent = lambda: be.from_numpy(np.zeros(0, dtype=np.int32))
+    A_rm, A_ent, L_rm, L_ent, U_rm, U_ent = rm(), ent(), rm(), ent(), rm(), ent()
+    kk.spiluk_symbolic(kh, 1, A_rm, A_ent, L_rm, L_ent, U_rm, U_ent)
+    assert ih.is_symbolic_complete() and (ih.get_nnzL(), ih.get_nnzU()) == (0, 0)
+    assert {k: ih.get(k) for k in ("num_levels", "launches", "max_level_rows", "plan_bytes")} == \
+        {"num_levels": 0, "launches": 0, "max_level_rows": 0, "plan_bytes": 8}
+    assert ih.export("level_list").shape == (0,) and ih.export("level_idx").shape == (0,)
+    assert np.array_equal(ih.export("level_ptr"), [0])
+    ih.set("chain_levels", 16)                              # plans again
+    assert ih.get("launches") == 0
+    val = lambda: be.from_numpy(np.zeros(0))
+    kk.spiluk_numeric(kh, 1, A_rm, A_ent, val(), L_rm, L_ent, val(), U_rm, U_ent, val())
+    assert be.lib.kkamd_spiluk_numeric(ih.h, 1, 0, *[None] * 9, 0, 1, None) == kk._capi.OK
+    kh.destroy_spiluk_handle()
+
+
 def _status(fn):
     kk = kk_loader.load()
     with pytest.raises(kk.KkamdError) as e:

@@ -78,6 +78,28 @@ def test_bidiagonal_is_one_chain_per_chain_levels():
     an.close()
 
 
+@pytest.mark.parametrize("algo", ["SEQLVLSCHD_RP", "SEQLVLSCHD_TP1CHAIN"])
+def test_empty_matrix(algo):
+    """0 rows: an analysis with no level, no launch and nothing kept on the device; the solve returns"""
+    kk, be = backend()
+    kh = kk.KokkosKernelsHandle(be)
+    kh.create_sptrsv_handle(algo, 0, True)
+    th = kh.get_sptrsv_handle()
+    row_map, entries = be.from_numpy(np.zeros(1, dtype=np.int32)), be.from_numpy(np.zeros(0, dtype=np.int32))
+    kk.sptrsv_symbolic(kh, row_map, entries)
+    assert th.is_symbolic_complete()
+    assert {k: th.get(k) for k in ("num_levels", "launches", "max_level_rows", "plan_bytes")} == \
+        {"num_levels": 0, "launches": 0, "max_level_rows": 0, "plan_bytes": 0}
+    for what in ("level_list", "nodes_per_level", "nodes_grouped_by_level"):
+        assert th.export(what).shape == (0,)
+    th.set("chain_levels", 16)                               # plans again
+    assert th.get("launches") == 0
+    val, b, x = (be.from_numpy(np.zeros(0)) for _ in range(3))
+    assert kk.sptrsv_solve(kh, row_map, entries, val, b, x) is x
+    assert be.lib.kkamd_sptrsv_solve(th.h, 0, None, None, None, None, None, 0, 1, None) == kk._capi.OK
+    kh.destroy_sptrsv_handle()
+
+
 def _status(fn):
     kk = kk_loader.load()
     with pytest.raises(kk.KkamdError) as e:
