@@ -506,6 +506,85 @@ int kkamd_spiluk_get(const kkamd_spiluk_handle_t* handle, const char* key, int64
 int kkamd_spiluk_export(const kkamd_spiluk_handle_t* handle, const char* what, void* h_out, int64_t count);
 
 /* ------------------------------------------------------------------------------------------------
+ * Point multicolor Gauss-Seidel.  Replaces KokkosSparse::gauss_seidel_symbolic / gauss_seidel_numeric / symmetric_gauss_seidel_apply /
+ * forward_sweep_gauss_seidel_apply / backward_sweep_gauss_seidel_apply for a CrsMatrix (sparse/src/KokkosSparse_gauss_seidel.hpp; handle
+ * sparse/src/KokkosSparse_gauss_seidel_handle.hpp; native implementation sparse/impl/KokkosSparse_gauss_seidel_impl.hpp: symbolic :697-830,
+ * the row update :159-179, point_apply :1401-1466, the sweep order :1496-1560).  A has num_rows rows and num_cols >= num_rows columns; the
+ * columns >= num_rows are ghost columns: read, never written, ignored by the colouring.  Every row stores its diagonal exactly once.
+ * int32 ordinals, int32 or int64 offsets, values F64 or F32.
+ *
+ * The colouring is Jones-Plassmann on the device with the priority pair (h(i), i), where for the 32-bit unsigned x = i
+ *     x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16;   h(i) = x      (arithmetic modulo 2^32)
+ * and (h(j), j) > (h(i), i) when h(j) > h(i), or h(j) == h(i) and j > i.  It equals the sequential greedy colouring (smallest colour no
+ * coloured neighbour holds) of the rows taken in descending priority: a function of the graph alone, the same on every run.
+ *
+ * The handle is the analogue of PointGaussSeidelHandle: colours, the permutation, the permuted matrix, the inverse diagonal, the permuted
+ * work vectors, and this library's knobs.  Not implemented: block / BSR Gauss-Seidel (block_gauss_seidel_*), GS_CLUSTER, GS_TWOSTAGE, the
+ * overloads that take execution-space instances (the _streams form of the handle), the reference-side TPL binding.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_gs_handle kkamd_gs_handle_t;
+/* KokkosSparse::GSAlgorithm (sparse/src/KokkosSparse_gauss_seidel_handle.hpp:30).  GS_DEFAULT, GS_PERMUTED and GS_TEAM run this
+ * implementation (GS_PERMUTED: one lane per row unless "lanes_per_row" is set); GS_CLUSTER and GS_TWOSTAGE: KKAMD_ERR_UNSUPPORTED */
+typedef enum {
+  KKAMD_GS_DEFAULT  = 0,
+  KKAMD_GS_PERMUTED = 1,
+  KKAMD_GS_TEAM     = 2,
+  KKAMD_GS_CLUSTER  = 3,
+  KKAMD_GS_TWOSTAGE = 4
+} kkamd_gs_algorithm;
+/* KokkosSparse::GSDirection (gauss_seidel_handle.hpp:31) */
+typedef enum { KKAMD_GS_FORWARD = 0, KKAMD_GS_BACKWARD = 1, KKAMD_GS_SYMMETRIC = 2 } kkamd_gs_direction;
+/* KokkosKernelsHandle::create_gs_handle(GSAlgorithm) / destroy_gs_handle (sparse/src/KokkosKernels_Handle.hpp:581-628,715-720) */
+int kkamd_gs_create(kkamd_gs_handle_t** handle, int algorithm);
+int kkamd_gs_destroy(kkamd_gs_handle_t* handle);
+/* gauss_seidel_symbolic(handle, num_rows, num_cols, row_map, entries, is_graph_symmetric) (sparse/src/KokkosSparse_gauss_seidel.hpp:45-134).
+ * Validates first (KKAMD_ERR_INVALID_ARG naming the smallest offending row: row map not ascending, a column outside [0, num_cols), no
+ * diagonal entry, more than one), colours the graph of the leading num_rows x num_rows block -- of A + A^T when is_graph_symmetric is 0 --
+ * groups the rows by colour (ascending inside a colour, the rows with more than "long_row_threshold" entries at the end of their colour,
+ * gauss_seidel_impl.hpp:787-810) and builds the permuted graph.  d_colors: NULL, or num_rows 1-based colours of the caller's (the reference
+ * lets the caller choose the colouring algorithm; this is the place for a known colouring such as red-black).  They are checked in one pass:
+ * a colour outside [1, num_rows] or two adjacent rows of one colour is KKAMD_ERR_INVALID_ARG naming the smallest offending row.
+ * May be repeated on one handle; a failed call leaves the handle without an analysis.  Synchronises the stream. */
+int kkamd_gs_symbolic(kkamd_gs_handle_t* handle, int64_t num_rows, int64_t num_cols, const void* d_row_map, const int32_t* d_entries,
+                      int offset_type, int is_graph_symmetric, const int32_t* d_colors, kkamd_stream_t stream);
+/* gauss_seidel_numeric(handle, num_rows, num_cols, row_map, entries, values[, given_inverse_diagonal], is_graph_symmetric)
+ * (gauss_seidel.hpp:173-370): gathers the values into the permuted order and stores 1 / a_ii per row, or d_inverse_diagonal (num_rows
+ * entries in the caller's row order; NULL = compute).  A zero diagonal gives Inf / NaN as in the reference.  KKAMD_ERR_STATE before a
+ * completed symbolic call.  May be repeated with new values.  Asynchronous on the stream. */
+int kkamd_gs_numeric(kkamd_gs_handle_t* handle, int64_t num_rows, int64_t num_cols, const void* d_row_map, const int32_t* d_entries,
+                     const void* d_values, const void* d_inverse_diagonal, int offset_type, int value_type, kkamd_stream_t stream);
+/* {symmetric,forward_sweep,backward_sweep}_gauss_seidel_apply(handle, num_rows, num_cols, row_map, entries, values, x, y, init_zero_x_vector,
+ * update_y_vector, omega, numIter) (gauss_seidel.hpp:372-760).  x has num_cols rows, y num_rows rows, both num_vecs >= 1 columns; element
+ * (i, v) is at d[i * row_stride + v * col_stride], so rank 1, LayoutLeft and LayoutRight are one entry point.  direction: a
+ * kkamd_gs_direction; one symmetric iteration is a forward sweep (colours 1..C) and then a backward sweep (C..1).  Every row update is
+ * x_i += omega * (y_i - sum_j a_ij x_j) * inv_diag_i with the diagonal term inside the sum (gauss_seidel_impl.hpp:159-179).
+ * Runs the numeric phase itself when none has run since the last symbolic call (:1473).  update_y = 0 reuses the permuted y of the
+ * previous apply: KKAMD_ERR_STATE when there is none or num_vecs changed.  init_zero_x != 0: x is not read, and all num_cols entries of x
+ * are written (ghost entries become 0, as in the reference).  KKAMD_ERR_STATE before a symbolic call.  Deterministic: no floating-point
+ * atomic, the same bits on every run and for every column whatever num_vecs is (columns go through the kernel in batches of 4). */
+int kkamd_gs_apply(kkamd_gs_handle_t* handle, int64_t num_rows, int64_t num_cols, const void* d_row_map, const int32_t* d_entries,
+                   const void* d_values, void* d_x, int64_t x_row_stride, int64_t x_col_stride, const void* d_y, int64_t y_row_stride,
+                   int64_t y_col_stride, int64_t num_vecs, int init_zero_x, int update_y, double omega, int num_iter, int direction,
+                   int offset_type, int value_type, kkamd_stream_t stream);
+/* Knobs (values outside the ranges: KKAMD_ERR_INVALID_ARG), the first three with the meaning and defaults of kkamd_sptrsv_set, a colour in
+ * the place of a level:
+ *   "lanes_per_row"       0 (default) = the smallest power of two that covers a quarter of the launch's mean row (about four entries per
+ *                         lane; measured), or 1, 2, 4, ..., 64
+ *   "chain_rows"          a colour with at most this many rows may join a chain; 0 = never; default 64
+ *   "chain_levels"        the most colours one chain launch covers (>= 1, default 1024)
+ *   "long_row_threshold"  PointGaussSeidelHandle::set_long_row_threshold (gauss_seidel_handle.hpp:346): rows with more entries go to the end
+ *                         of their colour and get one wave each; 0 (default) = none.  Read by the next symbolic call. */
+int kkamd_gs_set(kkamd_gs_handle_t* handle, const char* key, int value);
+/* "num_colors", "coloring_rounds" (0 for given colours), "num_rows", "num_cols", "symbolic_complete", "numeric_complete", "algorithm",
+ * "long_rows", "long_row_threshold", "tail_launches" (long-row launches of one sweep, beyond "launches"), "num_levels" (= num_colors),
+ * "max_level_rows", "launches" (colour and chain launches of one sweep), "chain_launches", "chained_levels", the three schedule knobs, and
+ * "plan_bytes": HBM the handle keeps, at most 48 num_rows + 12 nnz + 8 num_vecs (num_rows + num_cols) + 16 */
+int kkamd_gs_get(const kkamd_gs_handle_t* handle, const char* key, int64_t* value);
+/* to a HOST buffer of `count` int32: "colors" (num_rows entries, 1-based, original row order), "color_xadj" (num_colors + 1),
+ * "color_adj" (num_rows: the rows grouped by colour, which is the permutation new -> old), "old_to_new" (num_rows) */
+int kkamd_gs_export(const kkamd_gs_handle_t* handle, const char* what, void* h_out, int64_t count);
+
+/* ------------------------------------------------------------------------------------------------
  * Helpers either side of the path (KokkosSparse::sort_crs_matrix, sparse/src/KokkosSparse_SortCrs.hpp:43-120;
  * kk_exclusive_parallel_prefix_sum, common/src/KokkosKernels_SimpleUtils.hpp:86-135) and the synthetic
  * inputs of the benchmark configurations, generated in place in HBM

@@ -25,8 +25,13 @@ SPTRSV_EXPORTS = ["kkamd_sptrsv_create", "kkamd_sptrsv_destroy", "kkamd_sptrsv_s
 # ILU(k): bound when the loaded library exports it, like the triangular solve
 SPILUK_EXPORTS = ["kkamd_spiluk_create", "kkamd_spiluk_destroy", "kkamd_spiluk_symbolic", "kkamd_spiluk_numeric", "kkamd_spiluk_set",
                   "kkamd_spiluk_get", "kkamd_spiluk_export"]
+# multicolor Gauss-Seidel: bound when the loaded library exports it, like the triangular solve
+GS_EXPORTS = ["kkamd_gs_create", "kkamd_gs_destroy", "kkamd_gs_symbolic", "kkamd_gs_numeric", "kkamd_gs_apply", "kkamd_gs_set", "kkamd_gs_get",
+              "kkamd_gs_export"]
+GS_DEFAULT, GS_PERMUTED, GS_TEAM, GS_CLUSTER, GS_TWOSTAGE = range(5)
+GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = range(3)
 
-ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
+ALL_GATHER_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int,
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_void_p)
 
@@ -116,6 +121,16 @@ def bind(lib):
         lib.kkamd_spiluk_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
         lib.kkamd_spiluk_export.argtypes = [vp, C.c_char_p, vp, i64]
         names += SPILUK_EXPORTS
+    if hasattr(lib, "kkamd_gs_create"):
+        lib.kkamd_gs_create.argtypes = [C.POINTER(vp), ci]
+        lib.kkamd_gs_destroy.argtypes = [vp]
+        lib.kkamd_gs_symbolic.argtypes = [vp, i64, i64, vp, vp, ci, ci, vp, vp]
+        lib.kkamd_gs_numeric.argtypes = [vp, i64, i64, vp, vp, vp, vp, ci, ci, vp]
+        lib.kkamd_gs_apply.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64, i64, vp, i64, i64, i64, ci, ci, dbl, ci, ci, ci, ci, vp]
+        lib.kkamd_gs_set.argtypes = [vp, C.c_char_p, ci]
+        lib.kkamd_gs_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
+        lib.kkamd_gs_export.argtypes = [vp, C.c_char_p, vp, i64]
+        names += GS_EXPORTS
     for name in names:
         fn = getattr(lib, name)
         if name == "kkamd_dist_spgemm_handle":

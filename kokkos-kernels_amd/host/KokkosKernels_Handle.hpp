@@ -1,6 +1,6 @@
-// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV and SPILUK paths use
-// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862, spiluk :853-870): create / get / destroy of the
-// SpGEMM, SPTRSV and SPILUK sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
+// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV, SPILUK and Gauss-Seidel paths use
+// (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862, spiluk :853-870, gauss-seidel :538-544,581-628,
+// 715-720): create / get / destroy of the SpGEMM, SPTRSV, SPILUK and Gauss-Seidel sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
 // decision, like KOKKOSKERNELS_VERBOSE).  The team / vector / shared-memory / scheduling setters are HINTS in the reference
 // too -- its rocSPARSE and cuSPARSE paths take and ignore them, and its driver and unit tests set them before every spgemm
 // (perf_test/sparse/KokkosSparse_spgemm.cpp:311-317, sparse/unit_test/Test_Sparse_spgemm.hpp:91-92) -- so they are accepted,
@@ -10,6 +10,7 @@
 #include "KokkosSparse_spgemm_handle.hpp"
 #include "KokkosSparse_sptrsv_handle.hpp"
 #include "KokkosSparse_spiluk_handle.hpp"
+#include "KokkosSparse_gauss_seidel_handle.hpp"
 
 namespace KokkosKernels { namespace Experimental {
 
@@ -32,8 +33,12 @@ class KokkosKernelsHandle {
                                                                    TemporaryMemorySpace, PersistentMemorySpace>;
   using SPILUKHandleType = KokkosSparse::Experimental::SPILUKHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace,
                                                                    TemporaryMemorySpace, PersistentMemorySpace>;
+  using GaussSeidelHandleType = KokkosSparse::GaussSeidelHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
+                                                               PersistentMemorySpace>;
+  using PointGaussSeidelHandleType = KokkosSparse::PointGaussSeidelHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
+                                                                         PersistentMemorySpace>;
   KokkosKernelsHandle() = default;
-  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); }
+  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); destroy_gs_handle(); }
   KokkosKernelsHandle(const KokkosKernelsHandle&)            = delete;
   KokkosKernelsHandle& operator=(const KokkosKernelsHandle&) = delete;
 
@@ -73,6 +78,16 @@ class KokkosKernelsHandle {
   }
   void destroy_spiluk_handle() { delete spiluk_; spiluk_ = nullptr; }
 
+  // Gauss-Seidel sub-handle (:538-544,581-628,715-720).  The reference's second argument, the colouring algorithm, does not exist here:
+  // the library colours with its own deterministic Jones-Plassmann (include/kkamd.h).  GS_CLUSTER / GS_TWOSTAGE throw std::runtime_error.
+  GaussSeidelHandleType* get_gs_handle() { return gs_; }
+  PointGaussSeidelHandleType* get_point_gs_handle() { return gs_; }
+  void create_gs_handle(KokkosSparse::GSAlgorithm gs_algorithm = KokkosSparse::GS_DEFAULT) {
+    destroy_gs_handle();
+    gs_ = new PointGaussSeidelHandleType(gs_algorithm);
+  }
+  void destroy_gs_handle() { delete gs_; gs_ = nullptr; }
+
   // hints of the reference (:380-465; defaults :203-215): remembered, forwarded, without effect on gfx950
   void set_team_work_size(const int v) { team_work_size = v; hint("team_work_size", v); }
   int get_set_team_work_size() { return team_work_size; }
@@ -99,6 +114,7 @@ class KokkosKernelsHandle {
   SPGEMMHandleType* spgemm_ = nullptr;
   SPTRSVHandleType* sptrsv_ = nullptr;
   SPILUKHandleType* spiluk_ = nullptr;
+  PointGaussSeidelHandleType* gs_ = nullptr;
   bool verbose_             = false;
 };
 

@@ -323,6 +323,7 @@ class KokkosKernelsHandle:
         self._spgemm = None
         self._sptrsv = None
         self._spiluk = None
+        self._gs = None
 
     def create_spgemm_handle(self, algo="SPGEMM_KK"):
         """algo: a KokkosSparse::SPGEMMAlgorithm name (sparse/src/KokkosSparse_spgemm_handle.hpp:44-93).  SPGEMM_DEBUG / SPGEMM_SERIAL
@@ -372,6 +373,23 @@ class KokkosKernelsHandle:
         if self._spiluk is not None:
             self._spiluk.destroy()
         self._spiluk = None
+
+    def create_gs_handle(self, algo="GS_DEFAULT"):
+        """create_gs_handle(GSAlgorithm) (sparse/src/KokkosKernels_Handle.hpp:581-628); algo: a KokkosSparse::GSAlgorithm name
+        (sparse/src/KokkosSparse_gauss_seidel_handle.hpp:30).  GS_CLUSTER and GS_TWOSTAGE raise KkamdError(UNSUPPORTED)."""
+        self.backend = self.backend or torch_backend()
+        if algo not in _GS_ALGOS:
+            raise RuntimeError("Invalid GSAlgorithm name")
+        self.destroy_gs_handle()
+        self._gs = _GsHandle(self.backend, algo)
+
+    def get_gs_handle(self): return self._gs
+    def get_point_gs_handle(self): return self._gs
+
+    def destroy_gs_handle(self):
+        if self._gs is not None:
+            self._gs.destroy()
+        self._gs = None
 
 
 _SPTRSV_ALGOS = {"SEQLVLSCHD_RP": 0, "SEQLVLSCHD_TP1": 1, "SEQLVLSCHD_TP1CHAIN": 2, "SPTRSV_CUSPARSE": 3}
@@ -526,6 +544,110 @@ def spiluk_numeric(kh, fill_lev, A_row_map, A_entries, A_values, L_row_map, L_en
         if e.status == _capi.ERR_STATE:
             raise ValueError(str(e))   # std::invalid_argument in the reference
         raise
+
+
+_GS_ALGOS = {"GS_DEFAULT": 0, "GS_PERMUTED": 1, "GS_TEAM": 2, "GS_CLUSTER": 3, "GS_TWOSTAGE": 4}
+
+
+class _GsHandle(_LevelHandle):
+    """KokkosSparse::PointGaussSeidelHandle as far as the multicolor sweep uses it (sparse/src/KokkosSparse_gauss_seidel_handle.hpp):
+    algorithm, the colouring, the permutation, the long-row threshold, and this library's knobs (a colour is a level of the schedule).
+    export: "colors" (1-based), "color_xadj" (num_colors + 1), "color_adj" (the rows grouped by colour) or "old_to_new"."""
+    PER_LEVEL = {"color_xadj": 1}
+
+    def __init__(self, backend, algo):
+        super().__init__(backend, algo, "gs", _GS_ALGOS[algo])
+
+    def get_algorithm_type(self): return self.algo
+    def get_num_colors(self): return self.get("num_colors")
+    def is_numeric_called(self): return bool(self.get("numeric_complete"))
+    def set_long_row_threshold(self, lrt): self.set("long_row_threshold", lrt)
+    def get_long_row_threshold(self): return self.get("long_row_threshold")
+
+
+def gauss_seidel_symbolic(kh, num_rows, num_cols, row_map, entries, is_graph_symmetric=True, colors=None):
+    """KokkosSparse::gauss_seidel_symbolic(handle, num_rows, num_cols, row_map, entries, is_graph_symmetric)
+    (sparse/src/KokkosSparse_gauss_seidel.hpp:45-134): colours the graph on the device (of A + A^T unless is_graph_symmetric), groups
+    and permutes.  colors: None, or an int32 array of the caller's 1-based colours, validated.  May be repeated."""
+    gh = _sub_handle(kh, "get_gs_handle", "GS", "gauss_seidel_symbolic")
+    be, lib = gh.backend, gh.backend.lib
+    if int(row_map.shape[0]) != int(num_rows) + 1:
+        raise RuntimeError("KokkosSparse::gauss_seidel_symbolic: row_map has %d entries, not num_rows + 1 = %d" % (row_map.shape[0], num_rows + 1))
+    if colors is not None and (colors.shape[0] != num_rows or _np_dtype(colors) != np.dtype(np.int32)):
+        raise RuntimeError("KokkosSparse::gauss_seidel_symbolic: colors must hold num_rows int32 entries")
+    check(lib, lib.kkamd_gs_symbolic(gh.h, int(num_rows), int(num_cols), be.ptr(row_map), be.ptr(entries), _offset_type(row_map),
+                                     1 if is_graph_symmetric else 0, be.ptr(colors), be.stream()))
+
+
+def gauss_seidel_numeric(kh, num_rows, num_cols, row_map, entries, values, given_inverse_diagonal=None, is_graph_symmetric=True):
+    """KokkosSparse::gauss_seidel_numeric(handle, num_rows, num_cols, row_map, entries, values[, given_inverse_diagonal],
+    is_graph_symmetric) (sparse/src/KokkosSparse_gauss_seidel.hpp:173-370); a bool in the place of given_inverse_diagonal is the
+    reference's shorter overload.  New values need no second symbolic call."""
+    gh = _sub_handle(kh, "get_gs_handle", "GS", "gauss_seidel_numeric")
+    be, lib = gh.backend, gh.backend.lib
+    if isinstance(given_inverse_diagonal, bool):
+        given_inverse_diagonal = None
+    if given_inverse_diagonal is not None and (given_inverse_diagonal.shape[0] != num_rows or _np_dtype(given_inverse_diagonal) != _np_dtype(values)
+                                               or _vec_stride(given_inverse_diagonal, "gauss_seidel_numeric") != 1):
+        raise RuntimeError("KokkosSparse::gauss_seidel_numeric: given_inverse_diagonal must hold num_rows contiguous entries of the values' type")
+    try:
+        check(lib, lib.kkamd_gs_numeric(gh.h, int(num_rows), int(num_cols), be.ptr(row_map), be.ptr(entries), be.ptr(values),
+                                        be.ptr(given_inverse_diagonal), _offset_type(row_map), _scalar_type(values), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))
+        raise
+
+
+def _gs_apply(who, direction, kh, num_rows, num_cols, row_map, entries, values, x, y, init_zero_x_vector, update_y_vector, omega, num_iter):
+    gh = _sub_handle(kh, "get_gs_handle", "GS", who)
+    be, lib = gh.backend, gh.backend.lib
+    if y is None and not update_y_vector:
+        y = x[:num_rows]                                    # never read: the handle's permuted y of the previous apply is used
+    if len(x.shape) != len(y.shape) or len(x.shape) not in (1, 2):
+        raise RuntimeError("KokkosSparse::%s: x and y must both have rank 1 or both rank 2" % who)
+    nv = int(x.shape[1]) if len(x.shape) == 2 else 1
+    if x.shape[0] < num_cols or y.shape[0] < num_rows or (len(y.shape) == 2 and y.shape[1] != nv) or nv < 1:
+        raise RuntimeError("KokkosSparse::%s: Dimensions do not match: A: %d x %d, x: %s, y: %s" % (who, num_rows, num_cols, tuple(x.shape), tuple(y.shape)))
+    if _np_dtype(x) != _np_dtype(values) or _np_dtype(y) != _np_dtype(values):
+        raise RuntimeError("KokkosSparse::%s: values, x and y must have one scalar type" % who)
+    if len(x.shape) == 1:
+        xs, ys = (_vec_stride(x, who), 0), (_vec_stride(y, who), 0)
+    else:
+        xs, ys = _strides(x), _strides(y)
+        if min(xs) < 0 or min(ys) < 0:
+            raise RuntimeError("KokkosSparse::%s: negative strides are not supported" % who)
+    try:
+        check(lib, lib.kkamd_gs_apply(gh.h, int(num_rows), int(num_cols), be.ptr(row_map), be.ptr(entries), be.ptr(values), be.ptr(x), xs[0], xs[1],
+                                      be.ptr(y), ys[0], ys[1], nv, 1 if init_zero_x_vector else 0, 1 if update_y_vector else 0, float(omega),
+                                      int(num_iter), direction, _offset_type(row_map), _scalar_type(values), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))
+        raise
+    return x
+
+
+def symmetric_gauss_seidel_apply(kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec, y_rhs_input_vec, init_zero_x_vector=False,
+                                 update_y_vector=True, omega=1.0, numIter=1):
+    """KokkosSparse::symmetric_gauss_seidel_apply (sparse/src/KokkosSparse_gauss_seidel.hpp:372-500): numIter times a forward and then a
+    backward sweep, on the backend's current stream.  x: num_cols rows, y: num_rows rows, rank 1 or rank 2 in any layout."""
+    return _gs_apply("symmetric_gauss_seidel_apply", _capi.GS_SYMMETRIC, kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec,
+                     y_rhs_input_vec, init_zero_x_vector, update_y_vector, omega, numIter)
+
+
+def forward_sweep_gauss_seidel_apply(kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec, y_rhs_input_vec, init_zero_x_vector=False,
+                                     update_y_vector=True, omega=1.0, numIter=1):
+    """KokkosSparse::forward_sweep_gauss_seidel_apply (sparse/src/KokkosSparse_gauss_seidel.hpp:502-630): colours 1..C, numIter times"""
+    return _gs_apply("forward_sweep_gauss_seidel_apply", _capi.GS_FORWARD, kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec,
+                     y_rhs_input_vec, init_zero_x_vector, update_y_vector, omega, numIter)
+
+
+def backward_sweep_gauss_seidel_apply(kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec, y_rhs_input_vec, init_zero_x_vector=False,
+                                      update_y_vector=True, omega=1.0, numIter=1):
+    """KokkosSparse::backward_sweep_gauss_seidel_apply (sparse/src/KokkosSparse_gauss_seidel.hpp:632-760): colours C..1, numIter times"""
+    return _gs_apply("backward_sweep_gauss_seidel_apply", _capi.GS_BACKWARD, kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec,
+                     y_rhs_input_vec, init_zero_x_vector, update_y_vector, omega, numIter)
 
 
 def spgemm_symbolic(kh, A, transposeA, B, transposeB, Cmat=None, allocate=True):
