@@ -1,5 +1,6 @@
 /* kkamd.h -- C ABI of libkkamd.so: the MI355X (gfx950) native implementation of the
- * KokkosSparse::spmv / KokkosSparse::spgemm / KokkosSparse::sptrsv / KokkosSparse::spiluk hot path.
+ * KokkosSparse::spmv / KokkosSparse::spgemm / KokkosSparse::sptrsv / KokkosSparse::spiluk / KokkosSparse::gauss_seidel /
+ * KokkosSparse::Experimental::gmres hot path.
  *
  * This is the drop-in boundary.  It sits exactly where kokkos-kernels plugs vendor libraries in
  * today -- the "TPL specialisation" layer -- and takes what those specialisations hand over:
@@ -38,7 +39,8 @@ typedef enum {
   KKAMD_ERR_UNSUPPORTED  = 2, /* type tuple or mode not implemented here: caller diverts to native path  */
   KKAMD_ERR_HIP          = 3, /* a HIP runtime call failed (reference: *_SAFE_CALL -> std::runtime_error)*/
   KKAMD_ERR_ALLOC        = 4,
-  KKAMD_ERR_STATE        = 5  /* handle misuse, e.g. numeric before symbolic (std::invalid_argument)    */
+  KKAMD_ERR_STATE        = 5, /* handle misuse, e.g. numeric before symbolic (std::invalid_argument)    */
+  KKAMD_ERR_NUMERIC      = 6  /* a solver stopped on its numbers: GMRES breakdown, NaN residual (std::runtime_error) */
 } kkamd_status;
 
 typedef enum { KKAMD_F32 = 0, KKAMD_F64 = 1 } kkamd_scalar_type;
@@ -583,6 +585,90 @@ int kkamd_gs_get(const kkamd_gs_handle_t* handle, const char* key, int64_t* valu
 /* to a HOST buffer of `count` int32: "colors" (num_rows entries, 1-based, original row order), "color_xadj" (num_colors + 1),
  * "color_adj" (num_rows: the rows grouped by colour, which is the permutation new -> old), "old_to_new" (num_rows) */
 int kkamd_gs_export(const kkamd_gs_handle_t* handle, const char* what, void* h_out, int64_t count);
+
+/* ------------------------------------------------------------------------------------------------
+ * Preconditioners.  Replaces KokkosSparse::Experimental::Preconditioner<CRS> and its two implementations
+ * (sparse/src/KokkosSparse_Preconditioner.hpp:55-112, KokkosSparse_MatrixPrec.hpp:45-101, KokkosSparse_LUPrec.hpp:43-119).
+ * apply: y := alpha * M x + beta * y on n-vectors of the matrix's value type; beta == 0 does not read y.  The matrices' arrays are
+ * borrowed for the life of the preconditioner, as the reference's classes hold views.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_precond kkamd_precond_t;
+/* what the C++ virtual Preconditioner::apply binds to, and how a Gauss-Seidel or any foreign preconditioner comes in */
+typedef int (*kkamd_precond_fn)(void* ctx, const void* d_x, void* d_y, double alpha, double beta, int value_type, kkamd_stream_t stream);
+/* MatrixPrec(mat) (KokkosSparse_MatrixPrec.hpp:57-83): apply is spmv("N", alpha, M, x, beta, y) through a plan of its own */
+int kkamd_precond_create_matrix(kkamd_precond_t** p, const kkamd_crs_t* M, kkamd_stream_t stream);
+/* LUPrec(L, U) (KokkosSparse_LUPrec.hpp:64-101): y := alpha * U^-1 L^-1 x + beta * y with two kkamd_sptrsv handles (SEQLVLSCHD_TP1) that
+ * are analysed ONCE, here; the reference calls sptrsv_symbolic again at every apply (:94-98).  L with its (unit) diagonal stored, U with its
+ * diagonal stored, as kkamd_spiluk_numeric leaves them.  "LUPrec: L.numRows() != U.numRows()" is KKAMD_ERR_INVALID_ARG.  Synchronises
+ * the stream (the analysis returns counts); apply does not. */
+int kkamd_precond_create_lu(kkamd_precond_t** p, const kkamd_crs_t* L, const kkamd_crs_t* U, kkamd_stream_t stream);
+int kkamd_precond_create_callback(kkamd_precond_t** p, kkamd_precond_fn fn, void* ctx);
+/* Preconditioner::apply(X, Y, "N", alpha, beta) (KokkosSparse_Preconditioner.hpp:77-80); asynchronous on the stream */
+int kkamd_precond_apply(kkamd_precond_t* p, const void* d_x, void* d_y, double alpha, double beta, int value_type, kkamd_stream_t stream);
+int kkamd_precond_destroy(kkamd_precond_t* p);
+
+/* ------------------------------------------------------------------------------------------------
+ * Restarted GMRES with right preconditioning.  Replaces KokkosSparse::Experimental::gmres for a CrsMatrix
+ * (sparse/src/KokkosSparse_gmres.hpp:58-158; handle sparse/src/KokkosSparse_gmres_handle.hpp:38-181; the loop
+ * sparse/impl/KokkosSparse_gmres_impl.hpp:59-329, restated step for step on the host around the kernels of kk_gmres.hip).
+ * The handle is the analogue of GMRESHandle plus this library's workspace: the basis V (n (m + 1) values), four work vectors, the
+ * partial slabs of the deterministic reductions, the SpMV plan of the matrix last solved with; allocated at the first solve, kept while
+ * n, m and the value type stay.  Not implemented: BSR matrices, complex scalars, the reference-side TPL binding.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_gmres_handle kkamd_gmres_handle_t;
+/* GMRESHandle::Ortho and ::Flag (gmres_handle.hpp:76-89) */
+typedef enum { KKAMD_GMRES_CGS2 = 0, KKAMD_GMRES_MGS = 1 } kkamd_gmres_ortho;
+typedef enum { KKAMD_GMRES_CONV = 0, KKAMD_GMRES_NO_CONV = 1, KKAMD_GMRES_LOA = 2, KKAMD_GMRES_NOT_RUN = 3 } kkamd_gmres_flag;
+/* GMRESHandle(m = 50, tol = 1e-8, max_restart = 50) (gmres_handle.hpp:107-119): m <= 0 is KKAMD_ERR_INVALID_ARG with the reference's
+ * text "gmres: Please choose restart size m greater than zero." */
+int kkamd_gmres_create(kkamd_gmres_handle_t** handle, int64_t m, double tol, int64_t max_restart);
+int kkamd_gmres_destroy(kkamd_gmres_handle_t* handle);
+/* set_ortho / set_verbose / set_m / set_max_restart (gmres_handle.hpp:139-163) and this library's knobs:
+ *   "ortho" 0 CGS2 (default), 1 MGS; "verbose" 0 / 1: the reference's lines on stdout; "m"; "max_restart";
+ *   "fuse" 1 (default): the CGS2 step runs dot, fused update + dot, update + sum of squares, normalise (V read three times); 0: dot,
+ *          update, dot, update + sum of squares, normalise (four times).  Same grouping and lane order: identical bits;
+ *   "fuse_max_k" 1..64, default 17: with more columns than this the unfused pair runs whatever "fuse" says.  The default is the switch
+ *          point measured on MI355X: beyond it the fused kernel's LDS tile and its accumulators cost more occupancy
+ *          than the saved pass over V returns;
+ *   "rows_per_group" rows per workgroup of the reductions: 0 (default) = max(1024, ceil(n / 1024) rounded up to 256), or a multiple of
+ *          64 up to 2^24.  The bits of a result depend on n and this knob alone;
+ *   "profile" 0 (default) / 1: four events per iteration on the stream; kkamd_gmres_export then gives "precond_ms", "spmv_ms" and
+ *          "ortho_ms" (the orthogonalisation's kernels, without the copy of h), one value per iteration of the last solve. */
+int kkamd_gmres_set(kkamd_gmres_handle_t* handle, const char* key, int64_t value);
+int kkamd_gmres_set_tol(kkamd_gmres_handle_t* handle, double tol);
+/* reset_handle(m, tol, max_restart) (gmres_handle.hpp:121-130): also ortho = CGS2, verbose off, results back to NotRun */
+int kkamd_gmres_reset(kkamd_gmres_handle_t* handle, int64_t m, double tol, int64_t max_restart);
+/* "num_iters" (-1 before a solve), "conv_flag" (a kkamd_gmres_flag, NOT_RUN before a solve), "cycles", of the last solve "host_syncs"
+ * (stream synchronisations of the loop: one for the initial norms, one per CGS2 iteration -- j + 1 in MGS iteration j --, one per true
+ * residual check) and "launches" (its own kernels, SpMV and preconditioner not counted), "plan_bytes" (HBM the handle keeps, the SpMV
+ * plan included), the knobs, "last_fused" (1 when the last solve or kkamd_gmres_update ran the fused kernel),
+ * "num_short_residuals" / "num_true_residuals" (entries of the exports below), "num_rows" (of the workspace) */
+int kkamd_gmres_get(const kkamd_gmres_handle_t* handle, const char* key, int64_t* value);
+/* "end_rel_res" (get_end_rel_res, -1 before a solve) | "tol" */
+int kkamd_gmres_get_real(const kkamd_gmres_handle_t* handle, const char* key, double* value);
+/* to a HOST buffer of `count` doubles: "short_residuals" (shortRelRes of every iteration of the last solve), "true_residuals" (relRes of
+ * every evaluation: the initial one, then one per check), "hessenberg" (the un-rotated (m + 1) x m matrix of the last cycle, column-major),
+ * "basis" (n x (m + 1), column-major, of the last cycle; columns the cycle did not reach hold older data); under "profile" the three
+ * timing arrays (num_short_residuals entries each) */
+int kkamd_gmres_export(const kkamd_gmres_handle_t* handle, const char* what, double* h_out, int64_t count);
+/* gmres(handle, A, B, X, precond) (gmres.hpp:58-158).  d_b has A.num_rows entries, d_x A.num_cols (initial guess in, solution out); a
+ * matrix that is not square is the reference's "KokkosSparse::gmres: Dimensions do not match: ..." (:110-116), KKAMD_ERR_INVALID_ARG.
+ * Type pairs (F64,F64) and (F32,F32), else KKAMD_ERR_UNSUPPORTED.  precond: NULL or a right preconditioner, w = A (M v_j) and
+ * Xiter = X + M (V y) through apply(alpha = 1, beta = 1) (gmres_impl.hpp:150-155,249-252).  KKAMD_ERR_NUMERIC with the reference's text
+ * for a lucky breakdown without convergence (:219-223) and a NaN residual (:224-226; here also when the initial residual is NaN, which
+ * the reference reports as NoConv).  Synchronises the stream, because it returns counts. */
+int kkamd_gmres_solve(kkamd_gmres_handle_t* handle, const kkamd_crs_t* A, const void* d_b, void* d_x, kkamd_precond_t* precond, int vector_type,
+                      kkamd_stream_t stream);
+/* The building blocks, for a host with its own Arnoldi loop: V is n x k, column-major with column stride ldv >= n.
+ * _dot: d_h[0..k) = V^T w -- KokkosBlas::gemv("C", one, V0j, Wj, zero, Hj) (gmres_impl.hpp:168).
+ * _update: w_out = w_in + alpha * V h -- gemv("N") (:169; d_w_in NULL: w_out = alpha * V h; w_out may be w_in) -- and, when asked, from
+ * the updated vector d_h2[0..k) = V^T w_out (gemv("C"), :173) and *d_sumsq = sum w_out^2 (nrm2 squared, :183).  With "fuse" 1, d_h2 given
+ * and k <= "fuse_max_k" the update and the second product are one kernel.  Deterministic: the bits depend on n, k and "rows_per_group" alone.  Both
+ * synchronise the stream (their partial slab is a temporary). */
+int kkamd_gmres_dot(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, const void* d_V, int64_t ldv, const void* d_w, void* d_h, int value_type,
+                    kkamd_stream_t stream);
+int kkamd_gmres_update(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, double alpha, const void* d_V, int64_t ldv, const void* d_h,
+                       const void* d_w_in, void* d_w_out, void* d_h2, void* d_sumsq, int value_type, kkamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Helpers either side of the path (KokkosSparse::sort_crs_matrix, sparse/src/KokkosSparse_SortCrs.hpp:43-120;

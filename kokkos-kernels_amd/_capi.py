@@ -5,6 +5,7 @@ import ctypes as C
 F32, F64 = 0, 1
 I32, I64 = 0, 1
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_ALLOC, ERR_STATE = range(6)
+ERR_NUMERIC = 6
 SPMV_DEFAULT, SPMV_FAST_SETUP, SPMV_NATIVE, SPMV_MERGE_PATH, SPMV_NATIVE_MERGE_PATH = range(5)
 SPTRSV_SEQLVLSCHD_RP, SPTRSV_SEQLVLSCHD_TP1, SPTRSV_SEQLVLSCHD_TP1CHAIN, SPTRSV_CUSPARSE = range(4)
 SPILUK_SEQLVLSCHD_TP1 = 0
@@ -29,11 +30,22 @@ SPILUK_EXPORTS = ["kkamd_spiluk_create", "kkamd_spiluk_destroy", "kkamd_spiluk_s
 GS_EXPORTS = ["kkamd_gs_create", "kkamd_gs_destroy", "kkamd_gs_symbolic", "kkamd_gs_numeric", "kkamd_gs_apply", "kkamd_gs_set", "kkamd_gs_get",
               "kkamd_gs_export"]
 GS_DEFAULT, GS_PERMUTED, GS_TEAM, GS_CLUSTER, GS_TWOSTAGE = range(5)
+# restarted GMRES and the preconditioners: bound when the loaded library exports them, like the triangular solve
+GMRES_EXPORTS = ["kkamd_gmres_create", "kkamd_gmres_destroy", "kkamd_gmres_set", "kkamd_gmres_set_tol", "kkamd_gmres_reset", "kkamd_gmres_get",
+                 "kkamd_gmres_get_real", "kkamd_gmres_export", "kkamd_gmres_solve", "kkamd_gmres_dot", "kkamd_gmres_update",
+                 "kkamd_precond_create_matrix", "kkamd_precond_create_lu", "kkamd_precond_create_callback", "kkamd_precond_apply",
+                 "kkamd_precond_destroy"]
+GMRES_CGS2, GMRES_MGS = range(2)
+GMRES_CONV, GMRES_NO_CONV, GMRES_LOA, GMRES_NOT_RUN = range(4)
 GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = range(3)
 
 ALL_GATHER_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int,
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_void_p)
+
+
+# kkamd_precond_fn: (ctx, d_x, d_y, alpha, beta, value_type, stream) -> status
+PRECOND_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p)
 
 
 class Transport(C.Structure):
@@ -131,6 +143,24 @@ def bind(lib):
         lib.kkamd_gs_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
         lib.kkamd_gs_export.argtypes = [vp, C.c_char_p, vp, i64]
         names += GS_EXPORTS
+    if hasattr(lib, "kkamd_gmres_create"):
+        lib.kkamd_gmres_create.argtypes = [C.POINTER(vp), i64, dbl, i64]
+        lib.kkamd_gmres_destroy.argtypes = [vp]
+        lib.kkamd_gmres_set.argtypes = [vp, C.c_char_p, i64]
+        lib.kkamd_gmres_set_tol.argtypes = [vp, dbl]
+        lib.kkamd_gmres_reset.argtypes = [vp, i64, dbl, i64]
+        lib.kkamd_gmres_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
+        lib.kkamd_gmres_get_real.argtypes = [vp, C.c_char_p, C.POINTER(dbl)]
+        lib.kkamd_gmres_export.argtypes = [vp, C.c_char_p, vp, i64]
+        lib.kkamd_gmres_solve.argtypes = [vp, C.POINTER(CrsDesc), vp, vp, vp, ci, vp]
+        lib.kkamd_gmres_dot.argtypes = [vp, i64, i64, vp, i64, vp, vp, ci, vp]
+        lib.kkamd_gmres_update.argtypes = [vp, i64, i64, dbl, vp, i64, vp, vp, vp, vp, vp, ci, vp]
+        lib.kkamd_precond_create_matrix.argtypes = [C.POINTER(vp), C.POINTER(CrsDesc), vp]
+        lib.kkamd_precond_create_lu.argtypes = [C.POINTER(vp), C.POINTER(CrsDesc), C.POINTER(CrsDesc), vp]
+        lib.kkamd_precond_create_callback.argtypes = [C.POINTER(vp), PRECOND_FN, vp]
+        lib.kkamd_precond_apply.argtypes = [vp, vp, vp, dbl, dbl, ci, vp]
+        lib.kkamd_precond_destroy.argtypes = [vp]
+        names += GMRES_EXPORTS
     for name in names:
         fn = getattr(lib, name)
         if name == "kkamd_dist_spgemm_handle":

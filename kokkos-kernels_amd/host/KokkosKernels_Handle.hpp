@@ -1,4 +1,4 @@
-// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV, SPILUK and Gauss-Seidel paths use
+// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV, SPILUK, Gauss-Seidel and GMRES paths use
 // (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862, spiluk :853-870, gauss-seidel :538-544,581-628,
 // 715-720): create / get / destroy of the SpGEMM, SPTRSV, SPILUK and Gauss-Seidel sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
 // decision, like KOKKOSKERNELS_VERBOSE).  The team / vector / shared-memory / scheduling setters are HINTS in the reference
@@ -11,6 +11,7 @@
 #include "KokkosSparse_sptrsv_handle.hpp"
 #include "KokkosSparse_spiluk_handle.hpp"
 #include "KokkosSparse_gauss_seidel_handle.hpp"
+#include "KokkosSparse_gmres_handle.hpp"
 
 namespace KokkosKernels { namespace Experimental {
 
@@ -37,8 +38,10 @@ class KokkosKernelsHandle {
                                                                PersistentMemorySpace>;
   using PointGaussSeidelHandleType = KokkosSparse::PointGaussSeidelHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
                                                                          PersistentMemorySpace>;
+  using GMRESHandleType = KokkosSparse::Experimental::GMRESHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
+                                                                 PersistentMemorySpace>;
   KokkosKernelsHandle() = default;
-  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); destroy_gs_handle(); }
+  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); destroy_gs_handle(); destroy_gmres_handle(); }
   KokkosKernelsHandle(const KokkosKernelsHandle&)            = delete;
   KokkosKernelsHandle& operator=(const KokkosKernelsHandle&) = delete;
 
@@ -88,6 +91,14 @@ class KokkosKernelsHandle {
   }
   void destroy_gs_handle() { delete gs_; gs_ = nullptr; }
 
+  // GMRES sub-handle (reference: sparse/src/KokkosKernels_Handle.hpp, create_gmres_handle(m, tol, max_restart) / get / destroy)
+  GMRESHandleType* get_gmres_handle() { return gmres_; }
+  void create_gmres_handle(const size_type m = 50, const typename GMRESHandleType::float_t tol = 1e-8, const size_type max_restart = 50) {
+    destroy_gmres_handle();
+    gmres_ = new GMRESHandleType(m, tol, max_restart);
+  }
+  void destroy_gmres_handle() { delete gmres_; gmres_ = nullptr; }
+
   // hints of the reference (:380-465; defaults :203-215): remembered, forwarded, without effect on gfx950
   void set_team_work_size(const int v) { team_work_size = v; hint("team_work_size", v); }
   int get_set_team_work_size() { return team_work_size; }
@@ -115,6 +126,7 @@ class KokkosKernelsHandle {
   SPTRSVHandleType* sptrsv_ = nullptr;
   SPILUKHandleType* spiluk_ = nullptr;
   PointGaussSeidelHandleType* gs_ = nullptr;
+  GMRESHandleType* gmres_   = nullptr;
   bool verbose_             = false;
 };
 

@@ -324,6 +324,7 @@ class KokkosKernelsHandle:
         self._sptrsv = None
         self._spiluk = None
         self._gs = None
+        self._gmres = None
 
     def create_spgemm_handle(self, algo="SPGEMM_KK"):
         """algo: a KokkosSparse::SPGEMMAlgorithm name (sparse/src/KokkosSparse_spgemm_handle.hpp:44-93).  SPGEMM_DEBUG / SPGEMM_SERIAL
@@ -390,6 +391,20 @@ class KokkosKernelsHandle:
         if self._gs is not None:
             self._gs.destroy()
         self._gs = None
+
+    def create_gmres_handle(self, m=50, tol=1e-8, max_restart=50):
+        """create_gmres_handle(m, tol, max_restart) (sparse/src/KokkosKernels_Handle.hpp); m <= 0 raises ValueError with the reference's
+        text (std::invalid_argument, sparse/src/KokkosSparse_gmres_handle.hpp:116-118)"""
+        self.backend = self.backend or torch_backend()
+        self.destroy_gmres_handle()
+        self._gmres = GMRESHandle(self.backend, m, tol, max_restart)
+
+    def get_gmres_handle(self): return self._gmres
+
+    def destroy_gmres_handle(self):
+        if self._gmres is not None:
+            self._gmres.destroy()
+        self._gmres = None
 
 
 _SPTRSV_ALGOS = {"SEQLVLSCHD_RP": 0, "SEQLVLSCHD_TP1": 1, "SEQLVLSCHD_TP1CHAIN": 2, "SPTRSV_CUSPARSE": 3}
@@ -648,6 +663,187 @@ def backward_sweep_gauss_seidel_apply(kh, num_rows, num_cols, row_map, entries, 
     """KokkosSparse::backward_sweep_gauss_seidel_apply (sparse/src/KokkosSparse_gauss_seidel.hpp:632-760): colours C..1, numIter times"""
     return _gs_apply("backward_sweep_gauss_seidel_apply", _capi.GS_BACKWARD, kh, num_rows, num_cols, row_map, entries, values, x_lhs_output_vec,
                      y_rhs_input_vec, init_zero_x_vector, update_y_vector, omega, numIter)
+
+
+class GMRESHandle:
+    """KokkosSparse::Experimental::GMRESHandle (sparse/src/KokkosSparse_gmres_handle.hpp:38-181): m, tol, max_restart, ortho, verbose, the
+    results of the last solve, and this library's knobs ("fuse", "rows_per_group": kkamd_gmres_set) and workspace."""
+    ORTHO = {"CGS2": 0, "MGS": 1}
+    FLAGS = ("Conv", "NoConv", "LOA", "NotRun")
+
+    def __init__(self, backend, m=50, tol=1e-8, max_restart=50):
+        self.backend = backend
+        self.h = C.c_void_p()
+        try:
+            check(backend.lib, backend.lib.kkamd_gmres_create(C.byref(self.h), int(m), float(tol), int(max_restart)))
+        except _capi.KkamdError as e:
+            if e.status == _capi.ERR_INVALID_ARG:
+                raise ValueError(str(e))
+            raise
+
+    def set(self, key, value):
+        check(self.backend.lib, self.backend.lib.kkamd_gmres_set(self.h, key.encode(), int(value)))
+
+    def get(self, key):
+        v = C.c_int64()
+        check(self.backend.lib, self.backend.lib.kkamd_gmres_get(self.h, key.encode(), C.byref(v)))
+        return int(v.value)
+
+    def get_real(self, key):
+        v = C.c_double()
+        check(self.backend.lib, self.backend.lib.kkamd_gmres_get_real(self.h, key.encode(), C.byref(v)))
+        return float(v.value)
+
+    def export(self, what):
+        """"short_residuals", "true_residuals", "hessenberg" ((m + 1) x m) or "basis" (n x (m + 1)) of the last solve, as float64"""
+        m = self.get("m")
+        if what == "hessenberg":
+            shape = (m + 1, m) if self.get("num_short_residuals") or self.get("num_true_residuals") else (0, 0)
+        elif what == "basis":
+            shape = (self.get("num_rows"), m + 1)
+        elif what in ("precond_ms", "spmv_ms", "ortho_ms"):
+            shape = (self.get("num_short_residuals") if self.get("profile") else 0,)
+        else:
+            shape = (self.get("num_" + what),)
+        out = np.zeros(int(np.prod(shape)), dtype=np.float64)
+        check(self.backend.lib, self.backend.lib.kkamd_gmres_export(self.h, what.encode(), out.ctypes.data_as(C.c_void_p), out.size))
+        return out.reshape(shape, order="F")
+
+    def get_m(self): return self.get("m")
+    def set_m(self, m): self.set("m", m)
+    def get_max_restart(self): return self.get("max_restart")
+    def set_max_restart(self, r): self.set("max_restart", r)
+    def get_tol(self): return self.get_real("tol")
+    def set_tol(self, tol): check(self.backend.lib, self.backend.lib.kkamd_gmres_set_tol(self.h, float(tol)))
+    def get_ortho(self): return ("CGS2", "MGS")[self.get("ortho")]
+
+    def set_ortho(self, ortho):
+        if ortho not in self.ORTHO:
+            raise ValueError("Invalid argument for 'ortho'.  Please use 'CGS2' or 'MGS'.")
+        self.set("ortho", self.ORTHO[ortho])
+
+    def get_verbose(self): return bool(self.get("verbose"))
+    def set_verbose(self, v): self.set("verbose", 1 if v else 0)
+
+    def reset_handle(self, m=50, tol=1e-8, max_restart=50):
+        check(self.backend.lib, self.backend.lib.kkamd_gmres_reset(self.h, int(m), float(tol), int(max_restart)))
+
+    def get_conv_flag_val(self): return self.FLAGS[self.get("conv_flag")]
+
+    def get_num_iters(self):
+        """the reference asserts that a solve has run (gmres_handle.hpp:165-168)"""
+        if self.get_conv_flag_val() == "NotRun":
+            raise AssertionError("get_num_iters: GMRES was never run")
+        return self.get("num_iters")
+
+    def get_end_rel_res(self):
+        if self.get_conv_flag_val() == "NotRun":
+            raise AssertionError("get_end_rel_res: GMRES was never run")
+        return self.get_real("end_rel_res")
+
+    def destroy(self):
+        if self.h:
+            self.backend.lib.kkamd_gmres_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class Preconditioner:
+    """KokkosSparse::Experimental::Preconditioner (sparse/src/KokkosSparse_Preconditioner.hpp:55-112) over a kkamd_precond_t.  A subclass
+    that overrides apply_device(d_x, d_y, alpha, beta, value_type, stream) -- raw device pointers -- and calls _init_callback() is a
+    foreign preconditioner (kkamd_precond_create_callback)."""
+
+    def __init__(self, backend=None):
+        self.backend = backend or torch_backend()
+        self.p = C.c_void_p()
+        self._keep = ()
+
+    def _init_callback(self):
+        def tramp(ctx, d_x, d_y, alpha, beta, value_type, stream):
+            try:
+                return int(self.apply_device(d_x, d_y, alpha, beta, value_type, stream) or 0)
+            except _capi.KkamdError as e:
+                return e.status
+        self._fn = _capi.PRECOND_FN(tramp)
+        check(self.backend.lib, self.backend.lib.kkamd_precond_create_callback(C.byref(self.p), self._fn, None))
+
+    def apply(self, X, Y, transM="N", alpha=1.0, beta=0.0):
+        """Y := alpha * M X + beta * Y on the backend's current stream"""
+        if transM[0] not in "Nn":
+            raise RuntimeError("Preconditioner::apply only supports 'N' for transM")
+        if _np_dtype(X) != _np_dtype(Y) or X.shape[0] != Y.shape[0] or _vec_stride(X, "apply") != 1 or _vec_stride(Y, "apply") != 1:
+            raise RuntimeError("Preconditioner::apply: X and Y must be contiguous rank-1 arrays of one length and scalar type")
+        be = self.backend
+        check(be.lib, be.lib.kkamd_precond_apply(self.p, be.ptr(X), be.ptr(Y), float(alpha), float(beta), _scalar_type(X), be.stream()))
+        return Y
+
+    def isInitialized(self): return True
+    def isComputed(self): return True
+    def hasTransposeApply(self): return False
+
+    def destroy(self):
+        if self.p:
+            self.backend.lib.kkamd_precond_destroy(self.p)
+            self.p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class MatrixPrec(Preconditioner):
+    """KokkosSparse::Experimental::MatrixPrec (sparse/src/KokkosSparse_MatrixPrec.hpp:45-101): apply is an SpMV with the given matrix"""
+
+    def __init__(self, mat):
+        super().__init__(mat.backend)
+        self._keep = (mat,)
+        d = mat.desc()
+        check(self.backend.lib, self.backend.lib.kkamd_precond_create_matrix(C.byref(self.p), C.byref(d), self.backend.stream()))
+
+
+class LUPrec(Preconditioner):
+    """KokkosSparse::Experimental::LUPrec (sparse/src/KokkosSparse_LUPrec.hpp:43-119): Y := alpha * U^-1 L^-1 X + beta * Y.  The two
+    triangular solves are analysed once, here (the reference analyses at every apply, :94-98)."""
+
+    def __init__(self, L, U):
+        super().__init__(L.backend)
+        if L.numRows() != U.numRows():
+            raise RuntimeError("LUPrec: L.numRows() != U.numRows()")
+        self._keep = (L, U)
+        dl, du = L.desc(), U.desc()
+        check(self.backend.lib, self.backend.lib.kkamd_precond_create_lu(C.byref(self.p), C.byref(dl), C.byref(du), self.backend.stream()))
+
+
+def gmres(kh, A, B, X, precond=None):
+    """KokkosSparse::Experimental::gmres(handle, A, B, X, precond) (sparse/src/KokkosSparse_gmres.hpp:58-158): solves A X = B from the
+    initial guess in X with restarted GMRES, right-preconditioned when precond is given; results in the handle
+    (get_num_iters / get_end_rel_res / get_conv_flag_val).  Breakdown and a NaN residual raise RuntimeError with the reference's text."""
+    gh = _sub_handle(kh, "get_gmres_handle", "GMRES", "gmres")
+    be, lib = gh.backend, gh.backend.lib
+    if len(B.shape) != 1 or len(X.shape) != 1:
+        raise RuntimeError("gmres: B and X must have rank 1")
+    if X.shape[0] != B.shape[0] or A.numCols() != X.shape[0] or A.numRows() != B.shape[0]:
+        raise RuntimeError("KokkosSparse::gmres: Dimensions do not match: , A: %d x %d, x: %d, b: %d" % (A.numRows(), A.numCols(), X.shape[0], B.shape[0]))
+    if _vec_stride(B, "gmres") != 1 or _vec_stride(X, "gmres") != 1:
+        raise RuntimeError("KokkosSparse::gmres: B and X must be contiguous")
+    if _np_dtype(B) != _np_dtype(X):
+        raise RuntimeError("gmres: B and X must have one scalar type")
+    d = A.desc()
+    try:
+        check(lib, lib.kkamd_gmres_solve(gh.h, C.byref(d), be.ptr(B), be.ptr(X), precond.p if precond is not None else None, _scalar_type(X),
+                                         be.stream()))
+    except _capi.KkamdError as e:
+        if e.status in (_capi.ERR_INVALID_ARG, _capi.ERR_NUMERIC):
+            raise RuntimeError(str(e))
+        raise
+    return X
 
 
 def spgemm_symbolic(kh, A, transposeA, B, transposeB, Cmat=None, allocate=True):
