@@ -201,6 +201,8 @@ int kkamd_spmv_struct(const kkamd_crs_t* A, char mode, int stencil_type, int ndi
  *                       off -- measured equal to the planned stream kernel on C2 --, 1 on; "march_planes" planes per workgroup (20)
  *   kkamd_spmv_struct (global only): "struct_remap", "struct_group", "struct_strip" workgroup orders, all off
  *   "verbose" (global): 1 = the library reports what it chose on stdout
+ *   "mis2_lanes_per_vertex" (kkamd_set_default only): lanes per work-list vertex of the MIS-2 unit, 0 (default: from the mean degree) or
+ *          a power of two up to 64; see kkamd_graph_d2_mis.  No output depends on it
  *   SpGEMM (kkamd_set_default only) "spgemm_win_bits" (columns per LDS bitmap pass), "spgemm_emit_win_bits" (the same for the rows that
  *          walk their products again in the numeric phase; 0 = spgemm_win_bits), "spgemm_val_cap" (entries of C per value window),
  *          "spgemm_force_unsorted", "spgemm_emit_chunked" (test hooks for alternative code paths);
@@ -669,6 +671,70 @@ int kkamd_gmres_dot(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, const vo
                     kkamd_stream_t stream);
 int kkamd_gmres_update(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, double alpha, const void* d_V, int64_t ldv, const void* d_h,
                        const void* d_w_in, void* d_w_out, void* d_h2, void* d_sumsq, int value_type, kkamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Distance-2 maximal independent set, MIS-2 aggregation and explicit graph coarsening.  Replaces KokkosGraph::graph_d2_mis,
+ * graph_mis2_coarsen, graph_mis2_aggregate (graph/src/KokkosGraph_MIS2.hpp:24-87; native implementation
+ * graph/impl/KokkosGraph_Distance2MIS_impl.hpp: MIS2_FAST :30-470, MIS2_QUALITY :472-793, the aggregation :795-1114) and
+ * KokkosGraph::Experimental::graph_explicit_coarsen / graph_explicit_coarsen_with_inverse_map
+ * (graph/src/KokkosGraph_ExplicitCoarsening.hpp:35-92) for a symmetric CRS graph: int32 ordinals, int32 or int64 offsets, no values.
+ * The graph is borrowed.  Handle-less, as the reference's are free functions.  Columns >= num_verts are ignored everywhere; self-loops
+ * are harmless.  Symmetry is the caller's contract, as in the reference; it is not checked up front.
+ *
+ * The results are the reference's, exactly, and functions of the graph alone.  Statuses are 32-bit unsigned, IN_SET = 0,
+ * OUT_SET = 0xFFFFFFFF, nvBits = the bit length of num_verts + 1.  MIS2_FAST: in round r = 0, 1, ... every undecided row i takes
+ *     status(i) = (i + 1) | (hash(hash(i) ^ hash(r)) << nvBits)          (modulo 2^32; decremented when it equals OUT_SET)
+ * where, for a 32-bit unsigned v taken into the 64-bit unsigned x (xorshiftHash<uint32_t>, common/src/KokkosKernels_SimpleUtils.hpp:377-385),
+ *     x ^= x >> 12;  x ^= x << 25;  x ^= x >> 27;  hash(v) = the low 32 bits of ((x * 2685821657736338717 - 1) >> 16)   (modulo 2^64);
+ * every live column takes the minimum status over itself and its neighbours, IN_SET counting as OUT_SET; an undecided row becomes OUT_SET
+ * when a column of its closed neighbourhood is OUT_SET, else IN_SET when all of them carry its own status.  Decided rows and OUT_SET
+ * columns leave the work lists.  MIS2_QUALITY: the same round with the fixed statuses
+ *     status(i) = (i + 1) + ((uint32)(score(i) * (float)((1 << (32 - nvBits)) - 2)) << nvBits),
+ *     score(i) = (float)(deg(i) - minDeg) * (1.f / (float)(maxDeg - minDeg))    in fp32, deg = the row's stored length;
+ * when all degrees are equal the reference divides by zero and casts a NaN: here score = 0 (a documented difference,
+ * like the two below: the report of a graph that is not symmetric, and the defined order of the rows without compress).
+ *
+ * Validation: one pass checks that row_map ascends and that no entry is negative: KKAMD_ERR_INVALID_ARG naming the smallest offending
+ * row.  On a symmetric graph every round decides at least the undecided row of smallest status; a round that decides no row returns
+ * KKAMD_ERR_INVALID_ARG "graph is not symmetric" where the reference would not return.  No input makes the host loop run without bound.
+ *
+ * stats: NULL, or 8 values: [0] rounds of the first MIS-2, [1] rounds of the masked MIS-2 (0 without one), [2] host synchronisations,
+ * [3] kernel launches, [4] primary aggregates, [5] secondary aggregates, [6] vertices still unlabelled before phase 3, [7] bytes of
+ * scratch.  Host synchronisations: one per round (the surviving lengths) plus a constant per call:
+ *     graph_d2_mis, graph_mis2_coarsen: 2 + rounds;   graph_mis2_aggregate: 3 + rounds + masked rounds.
+ * Kernel launches per round: 4 (column statuses, row decisions, one scan of the workgroup counts, the move; 6 with more than 2048
+ * workgroups).  The knob kkamd_set_default("mis2_lanes_per_vertex", 0 | 1 | 2 | ... | 64) sets the lanes per work-list vertex, 0 (default)
+ * = the smallest power of two that gives a lane at most about four entries of the mean closed neighbourhood.  No output depends on it.
+ * num_verts == 0: an empty set, zero aggregates, no launch.
+ * ------------------------------------------------------------------------------------------------ */
+/* KokkosGraph::MIS2_Algorithm (KokkosGraph_MIS2.hpp:24), in the reference's order */
+typedef enum { KKAMD_MIS2_QUALITY = 0, KKAMD_MIS2_FAST = 1 } kkamd_mis2_algorithm;
+/* graph_d2_mis(rowmap, colinds, algo) (KokkosGraph_MIS2.hpp:31-49): the set in ascending vertex order into d_mis (num_verts int32 of
+ * room), its size into *num_in_set.  Any other algorithm: KKAMD_ERR_INVALID_ARG with the reference's "graph_d2_mis: invalid algorithm". */
+int kkamd_graph_d2_mis(int64_t num_verts, const void* d_row_map, int offset_type, const int32_t* d_entries, int algorithm, int32_t* d_mis,
+                       int64_t* num_in_set, int64_t* stats, kkamd_stream_t stream);
+/* secondary == 0: graph_mis2_coarsen(rowmap, colinds, numClusters) (KokkosGraph_MIS2.hpp:51-64); != 0: graph_mis2_aggregate
+ * (:66-79).  d_labels: num_verts int32.  Phase 1: MIS2_FAST, aggregate a = the a-th root in ascending order and its neighbours.  Phase 2
+ * (secondary only): the masked MIS2_FAST over the unlabelled vertices; a candidate with at least 3 unlabelled vertices in its closed
+ * neighbourhood becomes an aggregate, the ids continuing in ascending candidate order (a scan, no atomic counter).  Phase 3, from a
+ * frozen copy of the labels: every non-root vertex walks its entries in stored order, tracks up to 8 distinct neighbouring aggregates,
+ * stops at the ninth, and moves by: adjacent to a root > connectivity > smaller size, the first best winning.  On a symmetric graph every
+ * vertex ends labelled in [0, *num_aggregates). */
+int kkamd_graph_mis2_aggregate(int64_t num_verts, const void* d_row_map, int offset_type, const int32_t* d_entries, int secondary,
+                               int32_t* d_labels, int64_t* num_aggregates, int64_t* stats, kkamd_stream_t stream);
+/* graph_explicit_coarsen(fineRowmap, fineEntries, labels, numCoarseVerts, coarseRowmap, coarseEntries, compress) and
+ * graph_explicit_coarsen_with_inverse_map (KokkosGraph_ExplicitCoarsening.hpp:35-92).  Coarse row c holds the labels != c of the in-range
+ * neighbours of cluster c's vertices.  compress != 0: sorted and merged, exactly the reference's result.  compress == 0: the reference's
+ * order and duplicates depend on atomics and a 512-slot hash table; here the row is defined: the cluster's vertices in ascending order,
+ * their entries in stored order, every cross-cluster entry kept -- the same set per row, never more than nnz entries.
+ * d_coarse_row_map: num_coarse + 1 offsets of the fine offset type; d_coarse_entries: `capacity` int32 of room.  *coarse_nnz is the
+ * entry count; capacity < *coarse_nnz returns KKAMD_ERR_INVALID_ARG with the true count and writes nothing, so a first call with
+ * capacity 0 sizes the second.  d_inverse_offsets (num_coarse + 1) / d_inverse_labels (num_verts): NULL, or the vertices grouped by
+ * cluster, ascending inside a cluster (the reference leaves that order to an atomic).  A label outside [0, num_coarse):
+ * KKAMD_ERR_INVALID_ARG naming the smallest offending vertex.  Synchronises the stream. */
+int kkamd_graph_explicit_coarsen(int64_t num_verts, const void* d_row_map, int offset_type, const int32_t* d_entries, const int32_t* d_labels,
+                                 int64_t num_coarse, int compress, void* d_coarse_row_map, int32_t* d_coarse_entries, int64_t capacity,
+                                 int64_t* coarse_nnz, int32_t* d_inverse_offsets, int32_t* d_inverse_labels, kkamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Helpers either side of the path (KokkosSparse::sort_crs_matrix, sparse/src/KokkosSparse_SortCrs.hpp:43-120;

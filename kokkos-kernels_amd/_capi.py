@@ -38,6 +38,9 @@ GMRES_EXPORTS = ["kkamd_gmres_create", "kkamd_gmres_destroy", "kkamd_gmres_set",
 GMRES_CGS2, GMRES_MGS = range(2)
 GMRES_CONV, GMRES_NO_CONV, GMRES_LOA, GMRES_NOT_RUN = range(4)
 GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = range(3)
+# MIS-2, aggregation, explicit coarsening: bound when the loaded library exports them, like the triangular solve
+MIS2_EXPORTS = ["kkamd_graph_d2_mis", "kkamd_graph_mis2_aggregate", "kkamd_graph_explicit_coarsen"]
+MIS2_QUALITY, MIS2_FAST = range(2)
 
 ALL_GATHER_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int), C.c_int,
@@ -161,6 +164,11 @@ def bind(lib):
         lib.kkamd_precond_apply.argtypes = [vp, vp, vp, dbl, dbl, ci, vp]
         lib.kkamd_precond_destroy.argtypes = [vp]
         names += GMRES_EXPORTS
+    if hasattr(lib, "kkamd_graph_d2_mis"):
+        lib.kkamd_graph_d2_mis.argtypes = [i64, vp, ci, vp, ci, vp, C.POINTER(i64), C.POINTER(i64), vp]
+        lib.kkamd_graph_mis2_aggregate.argtypes = [i64, vp, ci, vp, ci, vp, C.POINTER(i64), C.POINTER(i64), vp]
+        lib.kkamd_graph_explicit_coarsen.argtypes = [i64, vp, ci, vp, vp, i64, ci, vp, vp, i64, C.POINTER(i64), vp, vp, vp]
+        names += MIS2_EXPORTS
     for name in names:
         fn = getattr(lib, name)
         if name == "kkamd_dist_spgemm_handle":

@@ -103,6 +103,8 @@ extern int g_struct_strip;        // kkamd_spmv_struct: lines per XCD strip of t
 extern int g_struct_group;        // kkamd_spmv_struct: grouped XCD order of the interior workgroups (0 = dispatch order)
 extern int g_struct_lds_pad_kb;  // measurement aid: extra dynamic LDS per interior workgroup (lowers occupancy)
 
+extern int g_mis2_lanes;          // kk_mis2.hip: lanes per work-list vertex (knob "mis2_lanes_per_vertex"; 0 = from the mean degree)
+
 template <class T> struct scalar_tag;
 template <> struct scalar_tag<float>  { static constexpr int value = KKAMD_F32; };
 template <> struct scalar_tag<double> { static constexpr int value = KKAMD_F64; };

@@ -1814,6 +1814,7 @@ static int build_analysis(kkamd_spmv_plan* p, const kkamd_crs_t* A, hipStream_t 
 
 SpmvTuning g_spmv_default;
 int g_verbose = 0;
+int g_mis2_lanes = 0;   // read by kk_mis2.hip; lives here, next to kkamd_set_default, because not every build links that unit
 
 #ifdef KK_EMU
 void trace_push(const char*) {}
@@ -1877,6 +1878,10 @@ int kkamd_set_default(const char* key, int value) {
   if (key && std::strcmp(key, "struct_strip") == 0) {
     if (value < 0) return kk::fail(KKAMD_ERR_INVALID_ARG, "struct_strip: %d is negative", value);
     kk::g_struct_strip = value; return KKAMD_OK;
+  }
+  if (key && std::strcmp(key, "mis2_lanes_per_vertex") == 0) {
+    if (value < 0 || value > 64 || (value & (value - 1))) return kk::fail(KKAMD_ERR_INVALID_ARG, "mis2_lanes_per_vertex: %d is not 0 or a power of two up to 64", value);
+    kk::g_mis2_lanes = value; return KKAMD_OK;
   }
 #ifdef KK_ABLATE
   if (key && std::strcmp(key, "struct_lds_pad_kb") == 0) { kk::g_struct_lds_pad_kb = value; return KKAMD_OK; }

@@ -912,6 +912,86 @@ def spgemm(A, transposeA, B, transposeB):
     return Cm
 
 
+_MIS2_ALGOS = {"MIS2_QUALITY": _capi.MIS2_QUALITY, "MIS2_FAST": _capi.MIS2_FAST}
+MIS2_STATS = ("rounds", "masked_rounds", "host_syncs", "launches", "primary_aggregates", "secondary_aggregates", "unlabelled_before_phase3",
+              "scratch_bytes")
+
+
+def mis2_algorithm_name(algo):
+    """KokkosGraph::mis2_algorithm_name (graph/src/KokkosGraph_MIS2.hpp:81-87)"""
+    return algo if algo in _MIS2_ALGOS else "*** Invalid MIS2 algo enum value.\n"
+
+
+def _mis2_graph(who, row_map, entries, backend):
+    be = backend or torch_backend()
+    if not hasattr(be.lib, "kkamd_graph_d2_mis"):
+        raise RuntimeError("KokkosGraph::%s: the loaded library does not export the MIS-2 unit" % who)
+    n = max(int(row_map.shape[0]) - 1, 0)
+    if _np_dtype(entries) != np.dtype(np.int32):
+        raise RuntimeError("KokkosGraph::%s: entries must be int32" % who)
+    return be, be.lib, n
+
+
+def graph_d2_mis(row_map, entries, algo="MIS2_FAST", backend=None, stats=None):
+    """KokkosGraph::graph_d2_mis<device>(rowmap, colinds, algo) (graph/src/KokkosGraph_MIS2.hpp:31-49): the vertices of a distance-2
+    maximal independent set of a symmetric graph, ascending.  stats: None, or a dict that receives the MIS2_STATS."""
+    be, lib, n = _mis2_graph("graph_d2_mis", row_map, entries, backend)
+    if algo not in _MIS2_ALGOS:
+        raise ValueError("graph_d2_mis: invalid algorithm")
+    mis = be.empty(max(n, 1), np.int32)
+    cnt = C.c_int64()
+    st = (C.c_int64 * 8)()
+    check(lib, lib.kkamd_graph_d2_mis(n, be.ptr(row_map), _offset_type(row_map), be.ptr(entries), _MIS2_ALGOS[algo], be.ptr(mis), C.byref(cnt), st,
+                                      be.stream()))
+    if stats is not None:
+        stats.update(zip(MIS2_STATS, list(st)))
+    return mis[:cnt.value]
+
+
+def _mis2_labels(who, secondary, row_map, entries, backend, stats):
+    be, lib, n = _mis2_graph(who, row_map, entries, backend)
+    labels = be.empty(max(n, 1), np.int32)
+    cnt = C.c_int64()
+    st = (C.c_int64 * 8)()
+    check(lib, lib.kkamd_graph_mis2_aggregate(n, be.ptr(row_map), _offset_type(row_map), be.ptr(entries), secondary, be.ptr(labels), C.byref(cnt), st,
+                                              be.stream()))
+    if stats is not None:
+        stats.update(zip(MIS2_STATS, list(st)))
+    return labels[:n], cnt.value
+
+
+def graph_mis2_coarsen(row_map, entries, backend=None, stats=None):
+    """KokkosGraph::graph_mis2_coarsen<device>(rowmap, colinds, numClusters) (graph/src/KokkosGraph_MIS2.hpp:51-64): (labels, numClusters)"""
+    return _mis2_labels("graph_mis2_coarsen", 0, row_map, entries, backend, stats)
+
+
+def graph_mis2_aggregate(row_map, entries, backend=None, stats=None):
+    """KokkosGraph::graph_mis2_aggregate<device>(rowmap, colinds, numAggregates) (graph/src/KokkosGraph_MIS2.hpp:66-79): (labels,
+    numAggregates), with the secondary aggregates of phase 2"""
+    return _mis2_labels("graph_mis2_aggregate", 1, row_map, entries, backend, stats)
+
+
+def graph_explicit_coarsen(row_map, entries, labels, num_coarse, compress=True, inverse_map=False, backend=None):
+    """KokkosGraph::Experimental::graph_explicit_coarsen / graph_explicit_coarsen_with_inverse_map
+    (graph/src/KokkosGraph_ExplicitCoarsening.hpp:35-92): (coarse_row_map, coarse_entries), with inverse_map also (inverse_offsets,
+    inverse_labels).  One call of the C entry point, with room for nnz entries: the documented upper bound of the coarse graph."""
+    be, lib, n = _mis2_graph("graph_explicit_coarsen", row_map, entries, backend)
+    nc = int(num_coarse)
+    if n and (int(labels.shape[0]) != n or _np_dtype(labels) != np.dtype(np.int32)):
+        raise RuntimeError("KokkosGraph::graph_explicit_coarsen: labels must hold num_verts int32 entries")
+    crm = be.empty(nc + 1, _np_dtype(row_map))
+    inv_off = be.empty(nc + 1, np.int32) if inverse_map else None
+    inv_lab = be.empty(max(n, 1), np.int32) if inverse_map else None
+    nnz = C.c_int64()
+    room = int(entries.shape[0])
+    cent = be.empty(max(room, 1), np.int32)
+    check(lib, lib.kkamd_graph_explicit_coarsen(n, be.ptr(row_map), _offset_type(row_map), be.ptr(entries), be.ptr(labels), nc, 1 if compress else 0,
+                                                be.ptr(crm), be.ptr(cent), room, C.byref(nnz), be.ptr(inv_off), be.ptr(inv_lab), be.stream()))
+    if inverse_map:
+        return crm, cent[:nnz.value], inv_off, inv_lab[:n]
+    return crm, cent[:nnz.value]
+
+
 def sort_crs_matrix(A):
     be, lib = A.backend, A.backend.lib
     check(lib, lib.kkamd_sort_crs(A.numRows(), be.ptr(A.graph.row_map), be.ptr(A.graph.entries),
