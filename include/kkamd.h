@@ -336,6 +336,43 @@ int kkamd_spgemm_numeric(kkamd_spgemm_handle_t* handle, int64_t m, int64_t n, in
                          int32_t* d_entriesC, void* d_valuesC, int offset_type, int value_type,
                          kkamd_stream_t stream);
 
+/* Jacobi-fused product, KokkosSparse::Experimental::spgemm_jacobi (sparse/src/KokkosSparse_spgemm_jacobi.hpp:26-188; semantics
+ * sparse/impl/KokkosSparse_spgemm_jacobi_seq_impl.hpp:65-123; what MueLu's SaPFactory reaches through Tpetra::MatrixMatrix::Jacobi):
+ *     C = (I - omega D^-1 A) B = B - omega D^-1 (A B),    A square (m == n), d_dinv = the m values 1 / a_ii, of the value type.
+ * Called in the place of kkamd_spgemm_numeric: kkamd_spgemm_symbolic(A, B) has completed on the handle, row_mapC is its output, entriesC and
+ * valuesC have c_nnz entries; rows of C leave column-sorted; the call may be repeated with new values, omega or dinv, and entries(C) are
+ * kept across calls as kkamd_spgemm_numeric keeps them ("entries_computed").  Statuses: those of kkamd_spgemm_numeric (KKAMD_ERR_STATE before
+ * the symbolic phase or with other dimensions, KKAMD_ERR_UNSUPPORTED for another value type); m != n, or a null d_dinv with c_nnz > 0:
+ * KKAMD_ERR_INVALID_ARG.
+ *
+ * Values.  With VT the value type and fl() one rounding to VT:
+ *     w      = VT(omega)
+ *     mult_i = fl(-w * dinv_i)
+ *     a'_ij  = fl(a_ij * mult_i)                                   for every stored entry of A (a buffer of nnz(A) values the handle owns)
+ *     N      = what kkamd_spgemm_numeric computes for (A', B) on this handle: the same kernels on the same bins (bit for bit the same
+ *              wherever one wave owns a row's accumulator; where several waves add into one with floating-point atomics, in the order
+ *              they arrive, as two calls of kkamd_spgemm_numeric differ from each other)
+ *     c_ik   = fl(N_ik + b_ik)                                     for every stored entry (i, k) of row i of B; a column stored several times
+ *                                                                  in the row is added once per copy, one after another in stored order
+ *     c_ik   = N_ik                                                everywhere else
+ * The reference's sequential form puts b_ik into the accumulator first and the products after it (its parallel forms define no order);
+ * here it joins last.  omega == 0 takes no shortcut (a'_ij = -0 * ..., signed zeros and NaN as the arithmetic gives them); Inf and NaN in
+ * A, B or dinv propagate as these five lines say.
+ *
+ * Pattern.  Every column of row i of B must occur in row i of C = pattern(A B).  It does whenever every row of A stores its diagonal.  The
+ * reference assumes it and writes past the row of C otherwise; here the call returns KKAMD_ERR_INVALID_ARG, the message naming the smallest
+ * such row, and values(C) are unspecified.
+ *
+ * Three steps on the stream, one synchronisation: a kernel writes a'; the numeric phase runs on (row_mapA, entriesA, a'); a kernel adds the
+ * rows of B, finding every column in its ascending row of C by bisection, without floating-point atomics.  When every row of B is strictly
+ * ascending (checked on the device in every call) a group of lanes shares a row -- about four entries of B's mean row per lane, 1..64 lanes --
+ * otherwise one lane walks each row in stored order.  kkamd_spgemm_get 24 / 25 and a "verbose" line say which. */
+int kkamd_spgemm_jacobi(kkamd_spgemm_handle_t* handle, int64_t m, int64_t n, int64_t k, const void* d_row_mapA,
+                        const int32_t* d_entriesA, const void* d_valuesA, const void* d_row_mapB,
+                        const int32_t* d_entriesB, const void* d_valuesB, const void* d_row_mapC,
+                        int32_t* d_entriesC, void* d_valuesC, double omega, const void* d_dinv /* m values of value_type */,
+                        int offset_type, int value_type, kkamd_stream_t stream);
+
 /* Options: what SPGEMMHandle / KokkosKernelsHandle setters map to (sparse/src/KokkosSparse_spgemm_handle.hpp:427-501,562-616;
  * sparse/src/KokkosKernels_Handle.hpp:380-465).  Set before the phase they shape.
  *   "algorithm"            SPGEMMAlgorithm value: SPGEMM_KK (default) and its aliases KK_MEMORY / KK_SPEED / KK_MEMSPEED / KK_LP run the
@@ -368,7 +405,8 @@ int kkamd_spgemm_set(kkamd_spgemm_handle_t* handle, const char* key, double valu
  * value kernel, 19 units (row of C, window of 2^18 columns) the last symbolic phase counted its dense class by (0: none, or row by row),
  * 20 units whose bitmap it kept for the numeric phase, 21 rows of the class whose every unit kept its structure (bitmap or entry list),
  * 22 bytes the process-wide store of kept structure holds at this moment, 23 the most it has held (process-wide; both are independent of
- * the handle passed; kkamd_release_scratch returns the store to the device).
+ * the handle passed; kkamd_release_scratch returns the store to the device), 24 lanes per row of B in the last kkamd_spgemm_jacobi call's
+ * epilogue, 25 that epilogue took the fast form (1: every row of B strictly ascending; 0: one lane per row, stored order).
  * With units, 12 counts the rows whose entries(C) the last numeric call wrote from kept units, 13 the rows held, 14 those of 12 with at
  * least one unit kept as an entry list. */
 int kkamd_spgemm_get(kkamd_spgemm_handle_t* handle, int what, int64_t* value);
@@ -381,7 +419,7 @@ int kkamd_spgemm_get_hint(kkamd_spgemm_handle_t* handle, const char* key, double
  *   _partition  contiguous slabs of near-equal MULTIPLICATIONS (row flops of sparse/impl/KokkosSparse_spgemm_impl_symbolic.hpp:1108-1185,
  *               computed on the device from the full A and B structure): fills row_offsets[world + 1] (host) and, when given,
  *               the multiplications of every slab; every rank that calls it with the same A and B gets the same answer.
- *   _symbolic / _numeric   kkamd_spgemm_symbolic / _numeric on the rank's slab (checked against the partition), state in the operator;
+ *   _symbolic / _numeric / _jacobi   kkamd_spgemm_symbolic / _numeric / _jacobi on the rank's slab (checked against the partition), state in the operator;
  *   _handle     the operator's SpGEMM handle, for kkamd_spgemm_set / _get;
  *   _query      "row0", "rows_local", "rows_global", "c_nnz_local", "mults_local". */
 typedef struct kkamd_dist_spgemm kkamd_dist_spgemm_t;
@@ -397,6 +435,12 @@ int kkamd_dist_spgemm_numeric(kkamd_dist_spgemm_t* op, int64_t m_local, int64_t 
                               const void* d_valuesA_local, const void* d_row_mapB, const int32_t* d_entriesB, const void* d_valuesB,
                               const void* d_row_mapC_local, int32_t* d_entriesC_local, void* d_valuesC_local, int offset_type, int value_type,
                               kkamd_stream_t stream);
+/* kkamd_spgemm_jacobi on the rank's slab: local row i of C adds global row row_offsets[rank] + i of the replicated B; d_dinv_local holds the
+ * slab's m_local inverse diagonals.  The global matrix must be square (n == the partition's rows).  No communication. */
+int kkamd_dist_spgemm_jacobi(kkamd_dist_spgemm_t* op, int64_t m_local, int64_t n, int64_t k, const void* d_row_mapA_local, const int32_t* d_entriesA_local,
+                             const void* d_valuesA_local, const void* d_row_mapB, const int32_t* d_entriesB, const void* d_valuesB,
+                             const void* d_row_mapC_local, int32_t* d_entriesC_local, void* d_valuesC_local, double omega, const void* d_dinv_local,
+                             int offset_type, int value_type, kkamd_stream_t stream);
 int kkamd_dist_spgemm_query(const kkamd_dist_spgemm_t* op, const char* key, int64_t* value);
 
 

@@ -64,7 +64,7 @@ def device_check():
     return name.value.decode(), bool(gfx.value), cus.value
 
 
-from .sparse import (CrsMatrix, SPMVHandle, KokkosKernelsHandle, spmv, spmv_struct, sort_and_merge_matrix, transpose_matrix, spgemm_symbolic, spgemm_numeric, spgemm,  # noqa: E402,F401
+from .sparse import (CrsMatrix, SPMVHandle, KokkosKernelsHandle, spmv, spmv_struct, sort_and_merge_matrix, transpose_matrix, spgemm_symbolic, spgemm_numeric, spgemm, spgemm_jacobi,  # noqa: E402,F401
                      sort_crs_matrix, laplace_matrix, Backend, torch_backend, sptrsv_symbolic, sptrsv_solve, spiluk_symbolic, spiluk_numeric,
                      gauss_seidel_symbolic, gauss_seidel_numeric, symmetric_gauss_seidel_apply, forward_sweep_gauss_seidel_apply,
                      backward_sweep_gauss_seidel_apply, GMRESHandle, Preconditioner, MatrixPrec, LUPrec, gmres,

@@ -13,12 +13,12 @@ SPILUK_SEQLVLSCHD_TP1 = 0
 EXPORTS = [
     "kkamd_last_error", "kkamd_version", "kkamd_device_info", "kkamd_trace_push", "kkamd_trace_pop", "kkamd_spmv_plan_create", "kkamd_spmv_plan_create_knobs", "kkamd_release_scratch", "kkamd_spmv_plan_destroy",
     "kkamd_spmv", "kkamd_spmv_mv", "kkamd_spmv_struct", "kkamd_sort_and_merge", "kkamd_transpose", "kkamd_spmv_plan_set", "kkamd_spmv_plan_values_changed", "kkamd_spmv_plan_query", "kkamd_spmv_plan_export", "kkamd_set_default", "kkamd_spgemm_create",
-    "kkamd_spgemm_destroy", "kkamd_spgemm_set", "kkamd_spgemm_symbolic", "kkamd_spgemm_numeric", "kkamd_spgemm_get", "kkamd_spgemm_get_hint", "kkamd_sort_crs",
+    "kkamd_spgemm_destroy", "kkamd_spgemm_set", "kkamd_spgemm_symbolic", "kkamd_spgemm_numeric", "kkamd_spgemm_jacobi", "kkamd_spgemm_get", "kkamd_spgemm_get_hint", "kkamd_sort_crs",
     "kkamd_exclusive_scan", "kkamd_gen_laplace", "kkamd_gen_laplace_rows", "kkamd_bench_read",
     "kkamd_dist_unique_id", "kkamd_dist_transport_selftest", "kkamd_dist_spmv_create", "kkamd_dist_spmv_destroy", "kkamd_dist_spmv_x_local", "kkamd_dist_spmv_apply",
     "kkamd_dist_spmv_query",
     "kkamd_dist_spgemm_partition", "kkamd_dist_spgemm_create", "kkamd_dist_spgemm_destroy", "kkamd_dist_spgemm_handle", "kkamd_dist_spgemm_symbolic",
-    "kkamd_dist_spgemm_numeric", "kkamd_dist_spgemm_query",
+    "kkamd_dist_spgemm_numeric", "kkamd_dist_spgemm_jacobi", "kkamd_dist_spgemm_query",
 ]
 # the sparse triangular solve: bound when the loaded library exports it (the emulator library of tests/emu/Makefile does not)
 SPTRSV_EXPORTS = ["kkamd_sptrsv_create", "kkamd_sptrsv_destroy", "kkamd_sptrsv_symbolic", "kkamd_sptrsv_solve", "kkamd_sptrsv_set",
@@ -94,6 +94,7 @@ def bind(lib):
     lib.kkamd_spgemm_set.argtypes = [vp, C.c_char_p, dbl]
     lib.kkamd_spgemm_symbolic.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, ci, C.POINTER(i64), vp]
     lib.kkamd_spgemm_numeric.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
+    lib.kkamd_spgemm_jacobi.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, vp, ci, ci, vp]
     lib.kkamd_spgemm_get.argtypes = [vp, ci, C.POINTER(i64)]
     lib.kkamd_spgemm_get_hint.argtypes = [vp, C.c_char_p, C.POINTER(dbl)]
     lib.kkamd_sort_crs.argtypes = [i64, vp, vp, vp, ci, ci, vp]
@@ -116,6 +117,7 @@ def bind(lib):
     lib.kkamd_dist_spgemm_handle.argtypes = [vp]
     lib.kkamd_dist_spgemm_symbolic.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, ci, C.POINTER(i64), vp]
     lib.kkamd_dist_spgemm_numeric.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp]
+    lib.kkamd_dist_spgemm_jacobi.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, vp, ci, ci, vp]
     lib.kkamd_dist_spgemm_query.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
     names = list(EXPORTS)
     if hasattr(lib, "kkamd_sptrsv_create"):

@@ -243,8 +243,9 @@ __global__ __launch_bounds__(kBlock) void spgemm_flops_long_kernel(const int32_t
 // among them with all its work-items (with 8 lanes on every row the hub rows of R-MAT scale 20 made this 1.9 ms of every symbolic phase;
 // streaming the entries with a search of the row map at every descent was fast there and 0.3 - 0.5 ms on stencils, whose rows end every
 // 7 - 27 entries; a bitmap of the row starts cost an allocation per call).
+// STRICT: a repeated column counts as unsorted too (spgemm_jacobi's epilogue: strictly ascending rows let lanes share a row without meeting).
 constexpr int kSortedLong = 256;
-template <class OffT>
+template <class OffT, bool STRICT = false>
 __global__ __launch_bounds__(kBlock) void rows_sorted_kernel(int64_t n, const OffT* __restrict__ rm,
                                                              const int32_t* __restrict__ ent, int* __restrict__ unsorted) {
   const int lane = threadIdx.x & 7;
@@ -252,11 +253,11 @@ __global__ __launch_bounds__(kBlock) void rows_sorted_kernel(int64_t n, const Of
   for (int64_t row = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / 8; row < n; row += (int64_t)gridDim.x * (kBlock / 8)) {
     const int64_t b = (int64_t)rm[row], e = (int64_t)rm[row + 1];
     if (e - b > kSortedLong) continue;
-    for (int64_t j = b + lane; j + 1 < e; j += 8) bad |= ent[j] > ent[j + 1];
+    for (int64_t j = b + lane; j + 1 < e; j += 8) bad |= STRICT ? ent[j] >= ent[j + 1] : ent[j] > ent[j + 1];
   }
   if (bad) *unsorted = 1;
 }
-template <class OffT>
+template <class OffT, bool STRICT = false>
 __global__ __launch_bounds__(kBlock) void rows_sorted_long_kernel(int64_t n, const OffT* __restrict__ rm, const int32_t* __restrict__ ent, int* __restrict__ unsorted) {
   __shared__ int s_long[kBlock];
   __shared__ int s_n;
@@ -272,9 +273,9 @@ __global__ __launch_bounds__(kBlock) void rows_sorted_long_kernel(int64_t n, con
     for (int64_t j = b + threadIdx.x; j + 1 < e; j += 8 * kBlock) {          // eight independent pairs per work-item and step
       int32_t x0[8], x1[8];
       KK_UNROLL
-      for (int u = 0; u < 8; ++u) { const int64_t q = j + u * kBlock; const bool in = q + 1 < e; x0[u] = in ? ent[q] : 0; x1[u] = in ? ent[q + 1] : 0; }
+      for (int u = 0; u < 8; ++u) { const int64_t q = j + u * kBlock; const bool in = q + 1 < e; x0[u] = in ? ent[q] : 0; x1[u] = in ? ent[q + 1] : 1; }     // (0, 1) past the row: in order under both comparisons
       KK_UNROLL
-      for (int u = 0; u < 8; ++u) bad |= x0[u] > x1[u];
+      for (int u = 0; u < 8; ++u) bad |= STRICT ? x0[u] >= x1[u] : x0[u] > x1[u];
     }
   }
   if (bad) *unsorted = 1;
@@ -3008,6 +3009,49 @@ __global__ __launch_bounds__(NT) void spgemm_item_vals_kernel(const ItemHead* __
   else { for (int i = t; i < ne; i += NT) valC[base + i] = sums[entC[base + i] - c0]; }
 }
 // ------------------------------------------------------------------------------------------------
+// spgemm_jacobi: C = B - omega D^-1 (A B) as the numeric phase on (row_mapA, entriesA, a') between two passes of its own.
+//   prologue  a'_ij = a_ij * mult_i, mult_i = -omega * dinv_i: 2^lg lanes per row, so dinv_i is read once per row and the row's values
+//             stream through adjacent lanes
+//   epilogue  c_ik += b_ik for the stored entries of row row0 + i of B: 2^lg lanes per row, every lane finds its column in the ascending
+//             row of C by bisection and adds with a plain read-add-write.  SORTED (rows of B strictly ascending): no two lanes of a row
+//             reach the same entry, and a lane's columns ascend, so its search starts behind its last hit.  !SORTED: launched with one
+//             lane per row, which walks the row in stored order -- the documented sequence of additions for repeated columns.
+//             Both forms are launched; *unsorted (written by rows_sorted_kernel<STRICT> earlier on the stream) says which one works,
+//             the other returns at once: the host learns the form after the call's one synchronisation, not between two.
+//             The first probes of a row's lanes fall on the same lines of entries(C), the last ones on neighbouring entries; a column
+//             that is not there leaves the smallest such row in *bad_row (the reference writes past the row instead).
+template <class OffT, class VT>
+__global__ __launch_bounds__(kBlock) void spgemm_jacobi_scale_kernel(int64_t m, int lg, const OffT* __restrict__ rmA, const VT* __restrict__ valA,
+                                                                     const VT* __restrict__ dinv, VT w, VT* __restrict__ out) {
+  const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x, row = gid >> lg;
+  if (row >= m) return;
+  const int64_t b = (int64_t)rmA[row], e = (int64_t)rmA[row + 1];
+  if (b >= e) return;
+  const VT mult = -w * dinv[row];
+  for (int64_t j = b + (gid & ((1 << lg) - 1)); j < e; j += (int64_t)1 << lg) out[j] = valA[j] * mult;
+}
+template <class OffT, class VT, bool SORTED>
+__global__ __launch_bounds__(kBlock) void spgemm_jacobi_add_kernel(int64_t m, int64_t row0, int lg, const OffT* __restrict__ rmB, const int32_t* __restrict__ entB,
+                                                                   const VT* __restrict__ valB, const OffT* __restrict__ rmC, const int32_t* __restrict__ entC,
+                                                                   VT* __restrict__ valC, const unsigned* __restrict__ unsorted, unsigned* __restrict__ bad_row) {
+  if ((*unsorted == 1u) == SORTED) return;
+  const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x, row = gid >> lg;
+  if (row >= m) return;
+  const int64_t bb = (int64_t)rmB[row0 + row], be = (int64_t)rmB[row0 + row + 1];
+  const int64_t cb = (int64_t)rmC[row], ce = (int64_t)rmC[row + 1];
+  int64_t from = cb;
+  bool missing = false;
+  for (int64_t j = bb + (gid & ((1 << lg) - 1)); j < be; j += (int64_t)1 << lg) {
+    const int32_t col = entB[j];
+    const VT v = valB[j];
+    int64_t lo = from, hi = ce;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (entC[mid] < col) lo = mid + 1; else hi = mid; }
+    if (lo < ce && entC[lo] == col) { valC[lo] = valC[lo] + v; if (SORTED) from = lo + 1; }
+    else missing = true;
+  }
+  if (missing) atomicMin(bad_row, (unsigned)row);
+}
+// ------------------------------------------------------------------------------------------------
 }  // namespace kk
 
 struct kkamd_spgemm_handle {
@@ -3078,6 +3122,10 @@ struct kkamd_spgemm_handle {
   bool tmp_taken = false;          // the running symbolic phase holds the process-wide buffer of temporaries (take_tmp)
   bool compressed = false;         // what the last symbolic call did
   int64_t compressed_mults = 0;
+  // spgemm_jacobi: two flags (16 bytes: B has an unsorted row, smallest row of B with a column outside C) and behind them the scaled values of
+  // A, nnz(A) of the value type; grown on demand, freed with the handle
+  void* d_jacobi = nullptr; size_t jacobi_bytes = 0;
+  int jacobi_lanes = 0; bool jacobi_fast = false;      // of the last epilogue (kkamd_spgemm_get 24, 25)
 };
 
 namespace kk {
@@ -4294,7 +4342,8 @@ static void numeric_report(const kkamd_spgemm_handle* h, const NumericRows& r) {
 template <class OffT, class VT>
 static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const void* rmA_, const int32_t* entA, const void* valA_,
                          const void* rmB_, const int32_t* entB, const void* valB_, const void* rmC_, int32_t* entC,
-                         void* valC_, hipStream_t st) {
+                         void* valC_, hipStream_t st, int (*tail)(void*, hipStream_t) = nullptr, void* tail_arg = nullptr) {
+  // tail: what a caller appends to the stream behind the value kernels and before the phase's synchronisation (spgemm_jacobi's epilogue)
   const NumericCall<OffT, VT> c = {k, (const OffT*)rmA_, entA, (const VT*)valA_, (const OffT*)rmB_, entB, (const VT*)valB_, (const OffT*)rmC_, entC, (VT*)valC_, st};
   int rc;
   if (!h->numeric_bins_ready && (rc = numeric_make_bins<OffT>(h, m, k, c.rmA, c.rmC, st))) return rc;
@@ -4317,6 +4366,7 @@ static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const voi
     if (!h->entries_reused && (rc = numeric_emit_entries(h, c))) return rc;
     if ((rc = numeric_launch_values(h, c, &acc, &rows))) return rc;
   }
+  if (tail && (rc = tail(tail_arg, st))) return rc;
   hipError_t e = hipGetLastError();
   hipError_t e2 = hipStreamSynchronize(st);   // the reference's numeric phase fences too (impl_kkmem.hpp:1440,1467)
   if (e != hipSuccess || e2 != hipSuccess) { h->entries_valid = false; return fail(KKAMD_ERR_HIP, "spgemm numeric failed: %s", hipGetErrorString(e != hipSuccess ? e : e2)); }
@@ -4324,6 +4374,109 @@ static int numeric_typed(kkamd_spgemm_handle* h, int64_t m, int64_t k, const voi
   if (h->verbose) numeric_report(h, rows);
   if (h->d_bm_store || h->unit_mode) { const int64_t used = h->bitmaps_used; free_bitmap_store(h); h->bitmaps_used = used; }    // entries(C) are written: the bitmaps (GBs) are not needed again
   return KKAMD_OK;
+}
+
+// ---- spgemm_jacobi -----------------------------------------------------------------------------------------------------------------
+// lanes per row, as a shift: the smallest power of two, 1..64, that leaves about four entries of the mean row to a lane (the rule of the
+// Gauss-Seidel sweeps and of MIS-2)
+static int jacobi_lanes_log2(int64_t entries, int64_t rows) {
+  const int64_t want = rows > 0 ? ceil_div(entries, 4 * rows) : 1;
+  int lg = 0;
+  while ((1 << lg) < kWave && (1 << lg) < want) ++lg;
+  return lg;
+}
+
+template <class OffT, class VT> struct JacobiEpilogue {
+  int64_t m, row0; int lg;
+  const OffT* rmB; const int32_t* entB; const VT* valB; const OffT* rmC; const int32_t* entC; VT* valC;
+  unsigned* d_flags; unsigned* h_flags;
+  // both forms behind one another (the one *unsorted does not name returns at once) and the flags' way to the host
+  static int launch(void* self, hipStream_t st) {
+    const JacobiEpilogue& q = *static_cast<const JacobiEpilogue*>(self);
+    if (q.m > 0) {
+      KK_LAUNCH((spgemm_jacobi_add_kernel<OffT, VT, true>), (unsigned)ceil_div(q.m << q.lg, kBlock), kBlock, 0, st, q.m, q.row0, q.lg, q.rmB, q.entB, q.valB,
+                q.rmC, (const int32_t*)q.entC, q.valC, (const unsigned*)q.d_flags, q.d_flags + 1);
+      KK_LAUNCH((spgemm_jacobi_add_kernel<OffT, VT, false>), (unsigned)ceil_div(q.m, kBlock), kBlock, 0, st, q.m, q.row0, 0, q.rmB, q.entB, q.valB,
+                q.rmC, (const int32_t*)q.entC, q.valC, (const unsigned*)q.d_flags, q.d_flags + 1);
+    }
+    KK_HIP(hipMemcpyAsync(q.h_flags, q.d_flags, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    return KKAMD_OK;
+  }
+};
+
+template <class OffT, class VT>
+static int jacobi_typed(kkamd_spgemm_handle* h, const char* who, int64_t m, int64_t k, int64_t row0, const void* rmA_, const int32_t* entA, const void* valA_,
+                        const void* rmB_, const int32_t* entB, const void* valB_, const void* rmC_, int32_t* entC, void* valC_, double omega,
+                        const void* dinv_, hipStream_t st) {
+  const OffT* rmA = (const OffT*)rmA_; const OffT* rmB = (const OffT*)rmB_;
+  const int64_t nnzA = h->c_nnz ? h->nnzA : 0;          // (an empty product: nothing to scale, nothing to multiply; B's rows are still looked up)
+  const size_t need = 16 + sizeof(VT) * (size_t)nnzA;
+  if (h->jacobi_bytes < need) {
+    if (h->d_jacobi) { (void)hipFree(h->d_jacobi); h->d_jacobi = nullptr; h->jacobi_bytes = 0; }
+    KK_HIP(hipMalloc(&h->d_jacobi, need));
+    h->jacobi_bytes = need;
+  }
+  unsigned* d_flags = reinterpret_cast<unsigned*>(h->d_jacobi);
+  VT* scaled = reinterpret_cast<VT*>(reinterpret_cast<char*>(h->d_jacobi) + 16);
+  KK_HIP(hipMemsetAsync(d_flags, 0xFF, 2 * sizeof(unsigned), st));           // "sorted so far", "no row so far"
+  // are the rows of B this call adds strictly ascending?  (Per call: the arrays of B are the caller's between calls.)
+  if (m > 0 && h->nnzB > 1) {
+    const int64_t nbk = ceil_div(m * 8, kBlock);
+    KK_LAUNCH((rows_sorted_kernel<OffT, true>), (unsigned)(nbk < 8192 ? nbk : 8192), kBlock, 0, st, m, rmB + row0, entB, reinterpret_cast<int*>(d_flags));
+    KK_LAUNCH((rows_sorted_long_kernel<OffT, true>), (unsigned)ceil_div(m, kBlock), kBlock, 0, st, m, rmB + row0, entB, reinterpret_cast<int*>(d_flags));
+  }
+  const int lgA = jacobi_lanes_log2(nnzA, m);
+  if (nnzA > 0)
+    KK_LAUNCH((spgemm_jacobi_scale_kernel<OffT, VT>), (unsigned)ceil_div(m << lgA, kBlock), kBlock, 0, st, m, lgA, rmA, (const VT*)valA_, (const VT*)dinv_, (VT)omega, scaled);
+  unsigned h_flags[2] = {0, 0};
+  JacobiEpilogue<OffT, VT> ep = {m, row0, jacobi_lanes_log2(h->nnzB, h->n), rmB, entB, (const VT*)valB_, (const OffT*)rmC_, entC, (VT*)valC_, d_flags, h_flags};
+  int rc;
+  if (h->c_nnz) {
+    rc = numeric_typed<OffT, VT>(h, m, k, rmA_, entA, scaled, rmB_, entB, valB_, rmC_, entC, valC_, st, &JacobiEpilogue<OffT, VT>::launch, &ep);
+  } else {
+    if ((rc = JacobiEpilogue<OffT, VT>::launch(&ep, st))) return rc;
+    hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    if (e != hipSuccess || e2 != hipSuccess) rc = fail(KKAMD_ERR_HIP, "%s failed: %s", who, hipGetErrorString(e != hipSuccess ? e : e2));
+  }
+  if (rc) return rc;
+  h->jacobi_fast = h_flags[0] != 1u; h->jacobi_lanes = h->jacobi_fast ? 1 << ep.lg : 1;
+  if (h->verbose)
+    KK_VERBOSE("\tkkamd spgemm jacobi: prologue %d lanes per row of A; epilogue %s, %d lanes per row of B\n", 1 << lgA,
+               h->jacobi_fast ? "fast form (rows of B strictly ascending)" : "general form (a row of B is unsorted or repeats a column: stored order)", h->jacobi_lanes);
+  if (h_flags[1] != 0xFFFFFFFFu)
+    return fail(KKAMD_ERR_INVALID_ARG, "%s: row %lld of B holds a column that row %lld of C does not have (every column of row i of B must occur in row i of A * B: "
+                "it does when every row of A stores its diagonal); values(C) are unspecified", who, (long long)(row0 + h_flags[1]), (long long)h_flags[1]);
+  return KKAMD_OK;
+}
+
+// the checks and the dispatch behind kkamd_spgemm_jacobi (row0 = -1: the whole matrix, m == n) and kkamd_dist_spgemm_jacobi (row0 >= 0: the slab's
+// first row in a square matrix of n rows)
+int spgemm_jacobi(kkamd_spgemm_handle* h, const char* who, int64_t m, int64_t n, int64_t k, int64_t row0, const void* d_row_mapA, const int32_t* d_entriesA,
+                  const void* d_valuesA, const void* d_row_mapB, const int32_t* d_entriesB, const void* d_valuesB, const void* d_row_mapC, int32_t* d_entriesC,
+                  void* d_valuesC, double omega, const void* d_dinv, int offset_type, int value_type, kkamd_stream_t stream) {
+  if (!h) return fail(KKAMD_ERR_STATE, "KokkosSparse::spgemm_jacobi: the given KernelHandle does not have an SpGEMM handle associated with it.");
+  if (!h->symbolic_called) return fail(KKAMD_ERR_STATE, "KokkosSparse::spgemm_jacobi: must first call spgemm_symbolic with the same handle.");
+  if (h->m != m || h->n != n || h->k != k || h->offset_type != offset_type)
+    return fail(KKAMD_ERR_STATE, "KokkosSparse::spgemm_jacobi: dimensions/offset type differ from the symbolic call on this handle.");
+  if (value_type != KKAMD_F32 && value_type != KKAMD_F64) return fail(KKAMD_ERR_UNSUPPORTED, "%s: unsupported value_type %d", who, value_type);
+  if (row0 < 0) {                                         // the whole matrix
+    if (m != n) return fail(KKAMD_ERR_INVALID_ARG, "%s: A is %lld x %lld: I - omega D^-1 A needs a square A", who, (long long)m, (long long)n);
+    row0 = 0;
+  }
+  if (row0 + m > n) return fail(KKAMD_ERR_INVALID_ARG, "%s: rows [%lld, %lld) of B are added to C, B has %lld", who, (long long)row0, (long long)(row0 + m), (long long)n);
+  h->numeric_called = true;
+  const bool look_up = m > 0 && h->nnzB > 0;              // some row of B may hold an entry
+  if (h->c_nnz == 0 && !look_up) return KKAMD_OK;
+  if (h->c_nnz > 0 && !d_dinv) return fail(KKAMD_ERR_INVALID_ARG, "%s: null dinv", who);
+  if (!d_row_mapB || !d_entriesB || !d_valuesB || !d_row_mapC || (h->c_nnz > 0 && (!d_valuesA || !d_entriesC || !d_valuesC || !d_entriesA || !d_row_mapA)))
+    return fail(KKAMD_ERR_INVALID_ARG, "%s: null pointer", who);
+  hipStream_t st = to_hip(stream);
+  TraceRange range(value_type == KKAMD_F64 ? "KokkosSparse::spgemm_jacobi[TPL_KKAMD,double]" : "KokkosSparse::spgemm_jacobi[TPL_KKAMD,float]");
+#define KK_JACOBI(OffT, VT) jacobi_typed<OffT, VT>(h, who, m, k, row0, d_row_mapA, d_entriesA, d_valuesA, d_row_mapB, d_entriesB, d_valuesB, d_row_mapC, d_entriesC, \
+                                                   d_valuesC, omega, d_dinv, st)
+  if (offset_type == KKAMD_I64) return value_type == KKAMD_F64 ? KK_JACOBI(int64_t, double) : KK_JACOBI(int64_t, float);
+  return value_type == KKAMD_F64 ? KK_JACOBI(int32_t, double) : KK_JACOBI(int32_t, float);
+#undef KK_JACOBI
 }
 
 int spgemm_set_default(const char* key, int value) {
@@ -4389,6 +4542,7 @@ int kkamd_spgemm_destroy(kkamd_spgemm_handle_t* h) {
   if (h->d_cidx) (void)hipFree(h->d_cidx);
   if (h->d_items_rank) (void)hipFree(h->d_items_rank);
   if (h->d_items_direct) (void)hipFree(h->d_items_direct);
+  if (h->d_jacobi) (void)hipFree(h->d_jacobi);
   delete h;
   // the last handle gone: the pooled store (GBs) goes back to the device unless the host asked to keep it ("spgemm_pool_keep")
   bool release = false;
@@ -4437,6 +4591,7 @@ int kkamd_spgemm_symbolic(kkamd_spgemm_handle_t* h, int64_t m, int64_t n, int64_
     nnzA = offset_type == KKAMD_I64 ? *(int64_t*)buf : (int64_t) * (int32_t*)buf;
     nnzB = offset_type == KKAMD_I64 ? *(int64_t*)(buf + 8) : (int64_t) * (int32_t*)(buf + 8);
   }
+  h->nnzA = nnzA; h->nnzB = nnzB;          // (of an empty product too: spgemm_jacobi still looks B's rows up in it)
   if (m == 0 || n == 0 || k == 0 || nnzA == 0 || nnzB == 0) {
     KK_HIP(hipMemsetAsync(d_row_mapC, 0, osz * (size_t)(m + 1), st));
     KK_HIP(hipStreamSynchronize(st));
@@ -4492,6 +4647,13 @@ int kkamd_spgemm_numeric(kkamd_spgemm_handle_t* h, int64_t m, int64_t n, int64_t
   return value_type == KKAMD_F64
              ? kk::numeric_typed<int32_t, double>(h, m, k, d_row_mapA, d_entriesA, d_valuesA, d_row_mapB, d_entriesB, d_valuesB, d_row_mapC, d_entriesC, d_valuesC, st)
              : kk::numeric_typed<int32_t, float>(h, m, k, d_row_mapA, d_entriesA, d_valuesA, d_row_mapB, d_entriesB, d_valuesB, d_row_mapC, d_entriesC, d_valuesC, st);
+}
+
+int kkamd_spgemm_jacobi(kkamd_spgemm_handle_t* h, int64_t m, int64_t n, int64_t k, const void* d_row_mapA, const int32_t* d_entriesA, const void* d_valuesA,
+                        const void* d_row_mapB, const int32_t* d_entriesB, const void* d_valuesB, const void* d_row_mapC, int32_t* d_entriesC, void* d_valuesC,
+                        double omega, const void* d_dinv, int offset_type, int value_type, kkamd_stream_t stream) {
+  return kk::spgemm_jacobi(h, "kkamd_spgemm_jacobi", m, n, k, -1, d_row_mapA, d_entriesA, d_valuesA, d_row_mapB, d_entriesB, d_valuesB, d_row_mapC, d_entriesC,
+                           d_valuesC, omega, d_dinv, offset_type, value_type, stream);
 }
 
 int kkamd_spgemm_set(kkamd_spgemm_handle_t* h, const char* key, double value) {
@@ -4581,6 +4743,8 @@ int kkamd_spgemm_get(kkamd_spgemm_handle_t* h, int what, int64_t* value) {
     case 21: *value = h->last_unit_rows_kept; break;  // rows of the class whose every unit kept its structure
     case 17: *value = h->n_items_rank; break;        // ... of which as position-indexed items / column-indexed blocks
     case 18: *value = h->n_items_direct; break;       // rows of the last numeric call's bins that take the column-block value kernel
+    case 24: *value = h->jacobi_lanes; break;         // lanes per row of B of the last spgemm_jacobi epilogue
+    case 25: *value = h->jacobi_fast ? 1 : 0; break;  // ... which took the fast form (rows of B strictly ascending)
     default: return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_spgemm_get: unknown query %d", what);
   }
   return KKAMD_OK;
@@ -4682,6 +4846,18 @@ int kkamd_dist_spgemm_numeric(kkamd_dist_spgemm_t* op, int64_t m_local, int64_t 
   if (rc) return rc;
   return kkamd_spgemm_numeric(op->h, m_local, n, k, d_row_mapA_local, d_entriesA_local, d_valuesA_local, d_row_mapB, d_entriesB, d_valuesB, d_row_mapC_local,
                               d_entriesC_local, d_valuesC_local, offset_type, value_type, stream);
+}
+int kkamd_dist_spgemm_jacobi(kkamd_dist_spgemm_t* op, int64_t m_local, int64_t n, int64_t k, const void* d_row_mapA_local, const int32_t* d_entriesA_local,
+                             const void* d_valuesA_local, const void* d_row_mapB, const int32_t* d_entriesB, const void* d_valuesB, const void* d_row_mapC_local,
+                             int32_t* d_entriesC_local, void* d_valuesC_local, double omega, const void* d_dinv_local, int offset_type, int value_type,
+                             kkamd_stream_t stream) {
+  const int rc = dist_spgemm_rows(op, m_local, "kkamd_dist_spgemm_jacobi");
+  if (rc) return rc;
+  if (op->offsets[(size_t)op->world] != n)
+    return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_dist_spgemm_jacobi: the partition has %lld rows, A has %lld columns: I - omega D^-1 A needs a square A",
+                    (long long)op->offsets[(size_t)op->world], (long long)n);
+  return kk::spgemm_jacobi(op->h, "kkamd_dist_spgemm_jacobi", m_local, n, k, op->offsets[(size_t)op->rank], d_row_mapA_local, d_entriesA_local, d_valuesA_local,
+                           d_row_mapB, d_entriesB, d_valuesB, d_row_mapC_local, d_entriesC_local, d_valuesC_local, omega, d_dinv_local, offset_type, value_type, stream);
 }
 int kkamd_dist_spgemm_query(const kkamd_dist_spgemm_t* op, const char* key, int64_t* value) {
   if (!op || !key || !value) return kk::fail(KKAMD_ERR_INVALID_ARG, "kkamd_dist_spgemm_query: null argument");

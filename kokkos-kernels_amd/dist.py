@@ -106,6 +106,19 @@ class DistSpgemm:
                                                            da.offset_type, da.value_type, be.stream()))
         return C_slab
 
+    def jacobi(self, A_slab, B, C_slab, omega, dinv_slab):
+        """the rank's slab of C = B - omega D^-1 (A B) (kkamd_dist_spgemm_jacobi): dinv_slab holds the slab's inverse diagonals"""
+        be = self.be
+        da, db, dc = A_slab.desc(), B.desc(), C_slab.desc()
+        seen = (id(self), id(C_slab.graph.entries), be.ptr(C_slab.graph.entries))
+        if getattr(C_slab, "_kk_numeric_seen", None) != seen:
+            self.set("entries_computed", 0)
+        C_slab._kk_numeric_seen = seen
+        check(self.lib, self.lib.kkamd_dist_spgemm_jacobi(self._op, A_slab.numRows(), A_slab.numCols(), B.numCols(), da.d_row_map, da.d_entries, da.d_values,
+                                                          db.d_row_map, db.d_entries, db.d_values, dc.d_row_map, dc.d_entries, dc.d_values,
+                                                          float(omega), be.ptr(dinv_slab), da.offset_type, da.value_type, be.stream()))
+        return C_slab
+
     def __del__(self):
         try:
             if self._op:

@@ -900,6 +900,36 @@ def spgemm_numeric(kh, A, transposeA, B, transposeB, Cmat):
     return Cmat
 
 
+def spgemm_jacobi(kh, A, transposeA, B, transposeB, Cmat, omega, dinv):
+    """KokkosSparse::Experimental::spgemm_jacobi (sparse/src/KokkosSparse_spgemm_jacobi.hpp:26-188) on matrices: C = B - omega D^-1 (A B) into
+    the C that spgemm_symbolic(kh, A, False, B, False) returned, in the place of spgemm_numeric.  dinv: A.numRows() values of A's value
+    type, rank 1 or rank 2 with one column."""
+    if transposeA or transposeB:
+        raise RuntimeError("spgemm-jacobi does not support transposed multiply. If you need this case please let kokkos-kernels developers know.\n")
+    sh = kh.get_spgemm_handle() if kh is not None else None
+    if sh is None:
+        raise ValueError("KokkosSparse::spgemm_jacobi: the given KernelHandle does not have an SpGEMM handle associated with it.")
+    be, lib = A.backend, A.backend.lib
+    if dinv is not None:
+        shape = tuple(int(v) for v in dinv.shape)
+        if shape not in ((A.numRows(),), (A.numRows(), 1)) or _np_dtype(dinv) != _np_dtype(A.values):
+            raise RuntimeError("KokkosSparse::spgemm_jacobi: dinv must hold A.numRows() values of A's value type (rank 1, or rank 2 with one column)")
+    seen = (id(sh), id(Cmat.graph.entries), be.ptr(Cmat.graph.entries))      # see spgemm_numeric: arrays not yet seen through this handle are new
+    if getattr(Cmat, "_kk_numeric_seen", None) != seen:
+        sh.set("entries_computed", 0)
+    try:
+        check(lib, lib.kkamd_spgemm_jacobi(sh.h, A.numRows(), A.numCols(), B.numCols(), be.ptr(A.graph.row_map), be.ptr(A.graph.entries), be.ptr(A.values),
+                                           be.ptr(B.graph.row_map), be.ptr(B.graph.entries), be.ptr(B.values), be.ptr(Cmat.graph.row_map),
+                                           be.ptr(Cmat.graph.entries), be.ptr(Cmat.values), float(omega), be.ptr(dinv),
+                                           _offset_type(A.graph.row_map), _scalar_type(A.values), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))   # std::invalid_argument in the reference
+        raise
+    Cmat._kk_numeric_seen = seen
+    return Cmat
+
+
 def spgemm(A, transposeA, B, transposeB):
     """No-reuse KokkosSparse::spgemm<CMatrix>(A, false, B, false) (sparse/src/KokkosSparse_spgemm.hpp:170-218)."""
     kh = KokkosKernelsHandle(A.backend)
