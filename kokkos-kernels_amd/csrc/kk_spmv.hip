@@ -249,9 +249,11 @@ __global__ __launch_bounds__(kBlock) void win_build_kernel(int64_t nnz, const in
 // tile belongs to segment g (its start sb_g <= i), j = i - (start of the segment's first row), row = j / L, k = j % L and
 // its x entry sits in LDS slot T_g[k] + row.  Per tile that is kPatW ints instead of 2 bytes per nonzero.  Tiles that do not
 // decompose into <= kPatSeg segments of rows with 1..kPatLen entries keep their 16-bit codes (nseg = 0).
-// Tile record (ints): [0] nseg, [1..kPatSeg-1] starts of segments 1.. (INT_MAX when unused; segment 0 starts at 0), [8 + 4g ..] {start,
-// -first row start, L, float 1 / L}, then the slot tables as signed 16-bit values (-1 <= slot < 4096): T_g[k] = short[32 g + k] behind
-// int kPatTab.  672 bytes per tile.
+// Tile record (ints): [0] nseg, [1..kPatSeg-1] starts of segments 1.. (INT_MAX when unused; segment 0 starts at 0), [8 + 4g ..] {first
+// virtual row (INT_MAX when unused; the tile's virtual rows are [head] + the rows that start in it, so segment 0 has 0), -first row start, L,
+// float 1 / L}, then the slot tables as signed 16-bit values (-1 <= slot < 4096): T_g[k] = short[32 g + k] behind
+// int kPatTab.  672 bytes per tile.  The record also fixes every row boundary inside the tile: virtual row j of segment g (first virtual row
+// q_g) holds the tile's nonzeros [(j - q_g) L_g - jadd_g, + L_g), clamped to the tile -- a pattern tile reads no row_map (pat_row_bounds).
 constexpr int kPatSeg = 8, kPatLen = 32, kPatRec = 8, kPatTab = kPatRec + 4 * kPatSeg, kPatW = kPatTab + kPatSeg * kPatLen / 2;
 
 template <class OffT, int NPT>
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(kBlock) void pat_build_kernel(int64_t nnz, const Of
       M  = 1.0f / (float)L;                                    // floor(j / L) = (int)((j + 0.5f) * M), exact for j < 2^16, L <= 32
     }
     if (t >= 1) out[t] = sb;                                  // starts of segments 1..7 (segment 0 starts at 0)
-    out[kPatRec + 4 * t + 0] = sb; out[kPatRec + 4 * t + 1] = -rs32; out[kPatRec + 4 * t + 2] = L32; out[kPatRec + 4 * t + 3] = __float_as_int(M);
+    out[kPatRec + 4 * t + 0] = t < nseg ? s_segq[t] : INT_MAX; out[kPatRec + 4 * t + 1] = -rs32; out[kPatRec + 4 * t + 2] = L32; out[kPatRec + 4 * t + 3] = __float_as_int(M);
   }
   if (t == 0) { out[0] = nseg; tinfo[b] = kTilePattern; }
   if (t < kPatSeg * kPatLen) {
@@ -493,7 +495,7 @@ __global__ __launch_bounds__(kBlock) void pat_direct_kernel(int64_t nnz, const O
       M  = 1.0f / (float)L;
     }
     if (t >= 1) out[t] = sb;
-    out[kPatRec + 4 * t + 0] = sb; out[kPatRec + 4 * t + 1] = -rs32; out[kPatRec + 4 * t + 2] = L32; out[kPatRec + 4 * t + 3] = __float_as_int(M);
+    out[kPatRec + 4 * t + 0] = t < nseg ? s_segq[t] : INT_MAX; out[kPatRec + 4 * t + 1] = -rs32; out[kPatRec + 4 * t + 2] = L32; out[kPatRec + 4 * t + 3] = __float_as_int(M);
   }
   if (t == 0) { out[0] = nseg; tinfo[b] = kTilePattern; }
   {
@@ -689,7 +691,7 @@ __device__ __forceinline__ void win_issue(const AT* __restrict__ values, const u
 // flight --; every work-item then picks its x entries out of LDS and the products replace them.
 template <class AT, class YT, int STEPS, bool PAT>
 __device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* __restrict__ x, int64_t ncols, YT* prod, int64_t b, int t,
-                                          const int32_t* __restrict__ pmeta) {
+                                          const int32_t* __restrict__ pmeta, int vrow, int& u0, int& u1) {
   // PAT (workgroup-uniform template choice made by the caller from the tile's mode): the tile has a row-pattern record and no codes
   constexpr int SPAN = kBlock * 2, NPT = 2 * STEPS, TILE = kBlock * NPT;
   constexpr int CAPC = WinGeom<STEPS>::CAPC, CPW = WinGeom<STEPS>::CPW;
@@ -730,10 +732,15 @@ __device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* _
     // (one grid line end inside) keep all four segments' constants in scalar registers too and select per nonzero by compares;
     // only tiles of five to eight segments read the constants of a nonzero's segment from the record in LDS.  Every branch
     // works in batches of 2 GRP nonzeros: all their table reads, then all their x reads -- no LDS round trip per nonzero.
+    // The same constants give the work-item the bounds [u0, u1) of its first-pass virtual row vrow (see pat_row_bounds): per-segment first
+    // virtual rows in scalar registers, and for five to eight segments the segment's constants from the record in LDS, read here, before
+    // the products overwrite it.
     if (nseg == 1) {
       const int jadd = pm[kPatRec + 1];
       const unsigned L = (unsigned)pm[kPatRec + 2];
       const float rcp  = __int_as_float(pm[kPatRec + 3]);
+      u0 = vrow * (int)L - jadd;
+      u1 = u0 + (int)L;
       KK_UNROLL
       for (int k = 0; k < STEPS; ++k) {
         KK_UNROLL
@@ -749,6 +756,13 @@ __device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* _
       const int ja0 = pm[kPatRec + 1], ja1 = pm[kPatRec + 5], ja2 = pm[kPatRec + 9], ja3 = pm[kPatRec + 13];
       const int sl0 = pm[kPatRec + 2], sl1 = pm[kPatRec + 6], sl2 = pm[kPatRec + 10], sl3 = pm[kPatRec + 14];
       const int sm0 = pm[kPatRec + 3], sm1 = pm[kPatRec + 7], sm2 = pm[kPatRec + 11], sm3 = pm[kPatRec + 15];
+      {
+        const int q1 = pm[kPatRec + 4], q2 = pm[kPatRec + 8], q3 = pm[kPatRec + 12];         // INT_MAX where the tile has fewer segments
+        const bool r1 = vrow >= q1, r2 = vrow >= q2, r3 = vrow >= q3;
+        const int q = r3 ? q3 : r2 ? q2 : r1 ? q1 : 0, ja = r3 ? ja3 : r2 ? ja2 : r1 ? ja1 : ja0, sl_ = r3 ? sl3 : r2 ? sl2 : r1 ? sl1 : sl0;
+        u0 = (vrow - q) * sl_ - ja;
+        u1 = u0 + sl_;
+      }
       KK_UNROLL
       for (int k0 = 0; k0 < STEPS; k0 += GRP) {
         int ti[2 * GRP], rw[2 * GRP], sl[2 * GRP];
@@ -774,6 +788,14 @@ __device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* _
       }
     } else {
       const int sb1 = pm[1], sb2 = pm[2], sb3 = pm[3], sb4 = pm[4], sb5 = pm[5], sb6 = pm[6], sb7 = pm[7];
+      {
+        int g = 0;
+        KK_UNROLL
+        for (int a = 1; a < kPatSeg; ++a) g += vrow >= pm[kPatRec + 4 * a];                  // INT_MAX where the tile has fewer segments
+        const int* rec = sseg + kPatRec + 4 * g;
+        u0 = (vrow - rec[0]) * rec[2] - rec[1];
+        u1 = u0 + rec[2];
+      }
       KK_UNROLL
       for (int k0 = 0; k0 < STEPS; k0 += GRP) {
         int ti[2 * GRP], rw[2 * GRP], sl[2 * GRP], ja[2 * GRP], sl_[2 * GRP], sm[2 * GRP];
@@ -817,6 +839,22 @@ __device__ __forceinline__ void win_stage(WinTile<AT, YT, STEPS>& W, const YT* _
     prod[li]     = (YT)v0[k] * x0[k];
     prod[li + 1] = (YT)v1[k] * x1[k];
   }
+}
+
+// Nonzeros [u0, u1) of virtual row j of a pattern tile, relative to the tile and not yet clamped to it (u0 < 0: the row starts in an
+// earlier tile, u1 > TILE: it ends in a later one), from the tile's record in memory: the words are wave-uniform (scalar loads), the
+// selection is per lane.  Integer arithmetic, exactly row_map[r] - s and row_map[r + 1] - s.  For the passes after the first of tiles with
+// more virtual rows than row groups; the first pass takes the same from the constants win_stage holds anyway.
+__device__ __forceinline__ void pat_row_bounds(const int32_t* __restrict__ pm, int j, int& u0, int& u1) {
+  int q = 0, ja = pm[kPatRec + 1], L = pm[kPatRec + 2];
+  KK_UNROLL
+  for (int g = 1; g < kPatSeg; ++g) {
+    const int qg = pm[kPatRec + 4 * g], jg = pm[kPatRec + 4 * g + 1], lg = pm[kPatRec + 4 * g + 2];
+    const bool in = j >= qg;                                   // unused segments: q_g = INT_MAX
+    q = in ? qg : q; ja = in ? jg : ja; L = in ? lg : L;
+  }
+  u0 = (j - q) * L - ja;
+  u1 = u0 + L;
 }
 
 // 32-bit halves of a scalar for lane permutes
@@ -906,7 +944,8 @@ template <class YT> __device__ __forceinline__ YT strided_lds_sum(const YT* prod
 // (one scalar load, one scalar wait) and the x chunks; (3) what else depends on the tile index alone -- pattern record, then the value
 // stream (with window meta, codes / entries where the mode has them); (4) the tile descriptor (first row + "starts inside a row"
 // flag: one scalar load) and with it the per-lane row bounds row_map[r], row_map[r+1] and, for beta != 0, the old y, which need
-// the descriptor but nothing from memory; (5) one vector-memory wait.  A pattern tile sees two scalar-cache reads and ONE
+// the descriptor but nothing from memory -- a pattern tile loads no row bounds: its record fixes them (pat_row_bounds), and they are
+// formed after the x pick from the constants that holds --; (5) one vector-memory wait.  A pattern tile sees two scalar-cache reads and ONE
 // vector-memory latency -- x is in LDS and the x pick under way while the values arrive --, and where its mode's tiles are
 // 0 ... n - 1 (list == null: the plan's list_identity) no list word in front.  Staged tiles without a record wait (counted) for
 // their vector meta before the x chunks, plain / code tiles for the columns before the x gathers: two vector-memory latencies.
@@ -985,13 +1024,14 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
   int64_t rc = r > 0 ? r : 0;
   rc         = rc < rb ? rc : rb - 1;                  // rb >= 1: row 0 starts before the end of any tile
   OffT rs_raw = OffT(0), re_raw = OffT(0);
-  if (!KK_ABL(16)) { rs_raw = row_map[rc]; re_raw = row_map[rc + 1]; }
+  if (MODE != kTilePattern && !KK_ABL(16)) { rs_raw = row_map[rc]; re_raw = row_map[rc + 1]; }     // a pattern tile's record holds its row bounds
+  int u0 = 0, u1 = 0;                                  // pattern tiles: the row's nonzeros relative to the tile, not yet clamped to it
   // beta != 0: the old y of the first pass' rows is requested now, with everything else, instead of right before the store
   YT yold = YT(0);
   if (beta != YT(0)) yold = y[rc];
 
   if (MODE >= kTileStaged) {
-    win_stage<AT, YT, STEPS, MODE == kTilePattern>(W, x, ncols, prod, b, t, pmeta);
+    win_stage<AT, YT, STEPS, MODE == kTilePattern>(W, x, ncols, prod, b, t, pmeta, grp, u0, u1);
   } else {
     if (full) stage_products<AT, YT, STEPS, true, true>(x, prod, t, v0, v1, c0, c1);
     else      stage_products<AT, YT, STEPS, false, false>(x, prod, t, v0, v1, c0, c1);
@@ -1007,11 +1047,13 @@ __global__ __launch_bounds__(kBlock) void spmv_stream3_kernel(int64_t nnz, const
     if (base > 0) {
       valid = (base + grp) < nv;
       r     = ra + base + grp - has_head;
-      if (valid) { rs = (int64_t)row_map[r]; re = (int64_t)row_map[r + 1]; }
+      if (MODE == kTilePattern) pat_row_bounds(pmeta + b * kPatW, (int)base + grp, u0, u1);
+      else if (valid) { rs = (int64_t)row_map[r]; re = (int64_t)row_map[r + 1]; }
     }
     const bool is_head  = r < ra;
-    const bool complete = !is_head && re <= e;
-    const int i0 = (int)((rs > s ? rs : s) - s), i1 = (int)((re < e ? re : e) - s);
+    const bool complete = !is_head && (MODE == kTilePattern ? u1 <= TILE : re <= e);
+    const int i0 = MODE == kTilePattern ? (u0 > 0 ? u0 : 0) : (int)((rs > s ? rs : s) - s);
+    const int i1 = MODE == kTilePattern ? (u1 < TILE ? u1 : TILE) : (int)((re < e ? re : e) - s);
     YT sum = valid ? (KK_ABL(8) ? prod[i0 < TILE ? i0 : 0] : strided_lds_sum<YT>(prod, i0, i1, lane, G)) : YT(0);
     sum = group_sum(sum, G);
     if (valid && lane == 0) {
