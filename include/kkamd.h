@@ -387,6 +387,9 @@ int kkamd_spgemm_jacobi(kkamd_spgemm_handle_t* handle, int64_t m, int64_t n, int
  *                          entries(C) again (re-allocated / overwritten arrays); 1 leaves the decision to the handle, which keeps
  *                          entries(C) across numeric calls only when it wrote them into the same row_map / entries arrays itself
  *                          (numeric reuse, sparse/tpls/KokkosSparse_spgemm_numeric_tpl_spec_decl.hpp:288-329)
+ *   "symbolic_computed"    0: the handle forgets its symbolic phase, so that the next kkamd_spgemm_symbolic analyses again even when it is
+ *                          given the same row map arrays (it otherwise answers a repeated call on the same arrays from memory, as the
+ *                          reference does): for a caller that rewrote those arrays in place with another pattern; 1 changes nothing
  * Hints -- accepted, recorded, reported under "verbose", without effect, exactly as the reference's rocSPARSE / cuSPARSE paths treat
  * them (the reference's driver and unit tests set them before every spgemm: perf_test/sparse/KokkosSparse_spgemm.cpp:311-317,378-399,
  * sparse/unit_test/Test_Sparse_spgemm.hpp:91-92): "team_work_size", "shmem_size", "suggested_team_size", "suggested_vector_size",
@@ -715,6 +718,97 @@ int kkamd_gmres_dot(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, const vo
                     kkamd_stream_t stream);
 int kkamd_gmres_update(kkamd_gmres_handle_t* handle, int64_t n, int64_t k, double alpha, const void* d_V, int64_t ldv, const void* d_h,
                        const void* d_w_in, void* d_w_out, void* d_h2, void* d_sumsq, int value_type, kkamd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Threshold incomplete LU by fixed-point iteration (ParILUT).  Replaces KokkosSparse::Experimental::par_ilut_symbolic / par_ilut_numeric
+ * (sparse/src/KokkosSparse_par_ilut.hpp:76-190, :207-380; handle sparse/src/KokkosSparse_par_ilut_handle.hpp:55-200; defaults
+ * sparse/src/KokkosKernels_Handle.hpp:871-881; the loop sparse/impl/KokkosSparse_par_ilut_numeric_impl.hpp:724-876, restated step for step
+ * around the kernels of kk_par_ilut.hip) for a square CrsMatrix whose rows are strictly ascending by column: int32 ordinals, int32 or int64
+ * offsets (one type for A, L and U), F64 or F32 values.  L leaves with a unit diagonal LAST in every row, U with its diagonal FIRST, rows
+ * ascending, as kkamd_precond_create_lu takes them.
+ * Not implemented: async_update = true (recorded and without effect, as in the reference, whose numeric phase forces it off:
+ * numeric_impl.hpp:740), BSR matrices, complex scalars, the reference-side TPL binding.
+ * NaN values give an unspecified pattern (std::nth_element on NaN is undefined in the reference too).
+ * Determinism: no floating-point atomics; the same bits on every run.  The bits depend on the lane count in use ("lanes_in_use": the knob
+ * "lanes_per_row", or with 0 what covers the mean row of A) because the dot products of the L chain and the residual's row sums are reduced
+ * across the lanes of a row; on nothing else.  The product L * U takes only its pattern from the SpGEMM: its values are summed in ascending k
+ * by a kernel of this unit, so rows of L * U of any length (the SpGEMM adds rows of more than 256 entries with floating-point atomics) leave
+ * the guarantee as it is.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct kkamd_par_ilut_handle kkamd_par_ilut_handle_t;
+/* PAR_ILUTHandle(max_iter = 20, residual_norm_delta_stop = 1e-2, fill_in_limit = 0.75, async_update = false, verbose = false)
+ * (par_ilut_handle.hpp:83-99; KokkosKernels_Handle.hpp:871-881).  max_iter < 0, fill_in_limit < 0 or a NaN: KKAMD_ERR_INVALID_ARG.  The
+ * handle owns one SpGEMM handle and every workspace; workspaces only grow. */
+int kkamd_par_ilut_create(kkamd_par_ilut_handle_t** handle, int64_t max_iter, double residual_norm_delta_stop, double fill_in_limit, int async_update,
+                          int verbose);
+int kkamd_par_ilut_destroy(kkamd_par_ilut_handle_t* handle);
+/* par_ilut_symbolic(handle, A_rowmap, A_entries, L_rowmap, U_rowmap) (par_ilut.hpp:76-190; symbolic_impl.hpp:36-93): row i of L gets
+ * 1 + #{col < i} entries, row i of U 1 + #{col > i}; both row maps (num_rows + 1 offsets) are scanned; nnzL, nnzU and num_rows go to the
+ * handle.  The graph is validated on the host before anything is indexed by it: a row map that does not ascend, a column outside
+ * [0, num_rows), a row that is not strictly ascending by column -- KKAMD_ERR_INVALID_ARG naming the smallest offending row; the last one
+ * carries the text the reference only asserts inside a kernel (numeric_impl.hpp:306, "is your A matrix sorted?").  Synchronises. */
+int kkamd_par_ilut_symbolic(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries, void* d_L_row_map,
+                            void* d_U_row_map, int offset_type, kkamd_stream_t stream);
+/* par_ilut_numeric(handle, A_rowmap, A_entries, A_values, L_rowmap, L_entries, L_values, U_rowmap, U_entries, U_values) (par_ilut.hpp:207-380;
+ * numeric_impl.hpp:724-876).  The sizes of the factors depend on the data (the reference resizes the caller's views every iteration), so
+ * the factors stay in the handle: the call writes the two FINAL row maps, "nnzL_out" / "nnzU_out" give the sizes and
+ * kkamd_par_ilut_copy_factors the entries and values.  The symbolic row maps are kept by the handle, so the call may be repeated with new
+ * values.  Before a completed symbolic call: KKAMD_ERR_STATE; another value type: KKAMD_ERR_UNSUPPORTED; num_rows or offset_type other than
+ * the symbolic call's: KKAMD_ERR_INVALID_ARG.  Synchronises the stream (sizes come back every iteration: "host_syncs"). */
+int kkamd_par_ilut_numeric(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries, const void* d_A_values,
+                           void* d_L_row_map, void* d_U_row_map, int offset_type, int value_type, kkamd_stream_t stream);
+/* The factors of the last numeric call, of its value type, on the stream.  A capacity below "nnzL_out" / "nnzU_out": KKAMD_ERR_INVALID_ARG
+ * with the true count, nothing written.  Before a completed numeric call: KKAMD_ERR_STATE. */
+int kkamd_par_ilut_copy_factors(kkamd_par_ilut_handle_t* handle, int32_t* d_L_entries, void* d_L_values, int64_t L_capacity, int32_t* d_U_entries,
+                                void* d_U_values, int64_t U_capacity, kkamd_stream_t stream);
+/* set_max_iter / set_residual_norm_delta_stop / set_fill_in_limit / set_async_update / set_verbose (par_ilut_handle.hpp:140-160):
+ *   "max_iter" >= 0; "residual_norm_delta_stop" (<= 0: no residual is computed and max_iter iterations run); "fill_in_limit" >= 0;
+ *   "async_update" 0 / 1, recorded, without effect; "verbose" 0 / 1: the reference's lines on stdout, from the host;
+ *   "lanes_per_row" 0 (default: what covers the mean row of A) or a power of two, 1..64;
+ *   "profile" 0 (default) / 1: the numeric phase synchronises the stream after every step and reads the host clock; kkamd_par_ilut_get_real
+ *          then gives "product_ms", "candidates_ms", "transpose_ms", "sweep_ms", "select_ms", "filter_ms" and "residual_ms", each summed
+ *          over the iterations of the last numeric call (a measurement aid: it changes no result).
+ * Values outside these ranges and unknown keys: KKAMD_ERR_INVALID_ARG. */
+int kkamd_par_ilut_set(kkamd_par_ilut_handle_t* handle, const char* key, double value);
+/* "num_iters" (get_num_iters, -1 before a numeric call), "nnzL", "nnzU", "num_rows" (of the symbolic call), "nnzL_out", "nnzU_out",
+ * "symbolic_complete", "numeric_complete", "max_iter", "async_update", "verbose", "lanes_per_row", "lanes_in_use",
+ * "stage_entries_per_lane", "plan_bytes" (HBM the handle holds, the SpGEMM handle's own not counted); of the last numeric call "host_syncs"
+ * (the synchronisations this unit issues itself: per iteration one for the candidate counts, one for the filtered counts and thresholds,
+ * one for the residual -- and one at the end; kkamd_spgemm_symbolic and kkamd_transpose synchronise inside in addition, and so does every
+ * hipMalloc / hipFree of a workspace that grows inside the loop: none of these is counted) and
+ * "launches" (its own kernels and scans; SpGEMM, transpose and sort not counted) and "max_product_row" (the longest row of L * U met) */
+int kkamd_par_ilut_get(const kkamd_par_ilut_handle_t* handle, const char* key, int64_t* value);
+/* "end_rel_res" (get_end_rel_res, -1 before a numeric call), the last "l_threshold" / "u_threshold", "residual_norm_delta_stop",
+ * "fill_in_limit", the seven step times of "profile" */
+int kkamd_par_ilut_get_real(const kkamd_par_ilut_handle_t* handle, const char* key, double* value);
+/* The steps of one iteration on caller-held device arrays, so that each can be tested alone.  The arrays are taken as the numeric phase holds
+ * them (sorted rows, columns in range, L's unit diagonal last, U's diagonal first) and are not validated.  They run with "lanes_per_row"
+ * lanes (0: 8) and synchronise the stream.
+ * _add_candidates (numeric_impl.hpp:129-328): L_new / U_new from A, the old L and U and LU = L * U.  Always writes the two row maps and
+ *   *nnzLn / *nnzUn; with both entry arrays NULL it stops there (the sizing call); a capacity too small is KKAMD_ERR_INVALID_ARG with the counts.
+ * _sweep (:354-458, compute_l_u_factors with async_update == false): renews L_values and U_values in place against the frozen Ut.
+ * _select (:480-494): the value of rank `rank` (0-based, ascending) among |values| into the device scalar d_threshold, by radix select;
+ *   exactly the order statistic (ties, zeros, -0.0, denormals, Inf).
+ * _filter (:496-597): keeps |v| >= *d_threshold or the diagonal, in stored order; sizing call with d_O_entries NULL as above.
+ * _residual (:602-668): sqrt(sum over A's pattern of (a - lu)^2), the sum in the value type, the square root on the host. */
+int kkamd_par_ilut_add_candidates(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries,
+                                  const void* d_A_values, const void* d_L_row_map, const int32_t* d_L_entries, const void* d_L_values,
+                                  const void* d_U_row_map, const int32_t* d_U_entries, const void* d_U_values, const void* d_LU_row_map,
+                                  const int32_t* d_LU_entries, const void* d_LU_values, int64_t nnzLU, void* d_Ln_row_map, int32_t* d_Ln_entries,
+                                  void* d_Ln_values, int64_t Ln_capacity, void* d_Un_row_map, int32_t* d_Un_entries, void* d_Un_values,
+                                  int64_t Un_capacity, int64_t* nnzLn, int64_t* nnzUn, int offset_type, int value_type, kkamd_stream_t stream);
+int kkamd_par_ilut_sweep(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries, const void* d_A_values,
+                         const void* d_L_row_map, const int32_t* d_L_entries, void* d_L_values, const void* d_U_row_map, const int32_t* d_U_entries,
+                         void* d_U_values, const void* d_Ut_row_map, const int32_t* d_Ut_entries, const void* d_Ut_values, int offset_type,
+                         int value_type, kkamd_stream_t stream);
+int kkamd_par_ilut_select(kkamd_par_ilut_handle_t* handle, int64_t count, const void* d_values, int64_t rank, void* d_threshold, int value_type,
+                          kkamd_stream_t stream);
+int kkamd_par_ilut_filter(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_I_row_map, const int32_t* d_I_entries, const void* d_I_values,
+                          const void* d_threshold, void* d_O_row_map, int32_t* d_O_entries, void* d_O_values, int64_t O_capacity, int64_t* nnz_out,
+                          int offset_type, int value_type, kkamd_stream_t stream);
+int kkamd_par_ilut_residual(kkamd_par_ilut_handle_t* handle, int64_t num_rows, const void* d_A_row_map, const int32_t* d_A_entries, const void* d_A_values,
+                            const void* d_LU_row_map, const int32_t* d_LU_entries, const void* d_LU_values, double* residual_norm, int offset_type,
+                            int value_type, kkamd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Distance-2 maximal independent set, MIS-2 aggregation and explicit graph coarsening.  Replaces KokkosGraph::graph_d2_mis,

@@ -65,7 +65,7 @@ def device_check():
 
 
 from .sparse import (CrsMatrix, SPMVHandle, KokkosKernelsHandle, spmv, spmv_struct, sort_and_merge_matrix, transpose_matrix, spgemm_symbolic, spgemm_numeric, spgemm, spgemm_jacobi,  # noqa: E402,F401
-                     sort_crs_matrix, laplace_matrix, Backend, torch_backend, sptrsv_symbolic, sptrsv_solve, spiluk_symbolic, spiluk_numeric,
+                     sort_crs_matrix, laplace_matrix, Backend, torch_backend, sptrsv_symbolic, sptrsv_solve, spiluk_symbolic, spiluk_numeric, par_ilut_symbolic, par_ilut_numeric,
                      gauss_seidel_symbolic, gauss_seidel_numeric, symmetric_gauss_seidel_apply, forward_sweep_gauss_seidel_apply,
                      backward_sweep_gauss_seidel_apply, GMRESHandle, Preconditioner, MatrixPrec, LUPrec, gmres,
                      graph_d2_mis, graph_mis2_coarsen, graph_mis2_aggregate, graph_explicit_coarsen, mis2_algorithm_name)

@@ -38,6 +38,11 @@ GMRES_EXPORTS = ["kkamd_gmres_create", "kkamd_gmres_destroy", "kkamd_gmres_set",
 GMRES_CGS2, GMRES_MGS = range(2)
 GMRES_CONV, GMRES_NO_CONV, GMRES_LOA, GMRES_NOT_RUN = range(4)
 GS_FORWARD, GS_BACKWARD, GS_SYMMETRIC = range(3)
+# ParILUT: bound when the loaded library exports it, like the triangular solve
+PAR_ILUT_EXPORTS = ["kkamd_par_ilut_create", "kkamd_par_ilut_destroy", "kkamd_par_ilut_symbolic", "kkamd_par_ilut_numeric",
+                    "kkamd_par_ilut_copy_factors", "kkamd_par_ilut_set", "kkamd_par_ilut_get", "kkamd_par_ilut_get_real",
+                    "kkamd_par_ilut_add_candidates", "kkamd_par_ilut_sweep", "kkamd_par_ilut_select", "kkamd_par_ilut_filter",
+                    "kkamd_par_ilut_residual"]
 # MIS-2, aggregation, explicit coarsening: bound when the loaded library exports them, like the triangular solve
 MIS2_EXPORTS = ["kkamd_graph_d2_mis", "kkamd_graph_mis2_aggregate", "kkamd_graph_explicit_coarsen"]
 MIS2_QUALITY, MIS2_FAST = range(2)
@@ -166,6 +171,21 @@ def bind(lib):
         lib.kkamd_precond_apply.argtypes = [vp, vp, vp, dbl, dbl, ci, vp]
         lib.kkamd_precond_destroy.argtypes = [vp]
         names += GMRES_EXPORTS
+    if hasattr(lib, "kkamd_par_ilut_create"):
+        lib.kkamd_par_ilut_create.argtypes = [C.POINTER(vp), i64, dbl, dbl, ci, ci]
+        lib.kkamd_par_ilut_destroy.argtypes = [vp]
+        lib.kkamd_par_ilut_symbolic.argtypes = [vp, i64, vp, vp, vp, vp, ci, vp]
+        lib.kkamd_par_ilut_numeric.argtypes = [vp, i64, vp, vp, vp, vp, vp, ci, ci, vp]
+        lib.kkamd_par_ilut_copy_factors.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
+        lib.kkamd_par_ilut_set.argtypes = [vp, C.c_char_p, dbl]
+        lib.kkamd_par_ilut_get.argtypes = [vp, C.c_char_p, C.POINTER(i64)]
+        lib.kkamd_par_ilut_get_real.argtypes = [vp, C.c_char_p, C.POINTER(dbl)]
+        lib.kkamd_par_ilut_add_candidates.argtypes = [vp, i64] + [vp] * 12 + [i64, vp, vp, vp, i64, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, ci, vp]
+        lib.kkamd_par_ilut_sweep.argtypes = [vp, i64] + [vp] * 12 + [ci, ci, vp]
+        lib.kkamd_par_ilut_select.argtypes = [vp, i64, vp, i64, vp, ci, vp]
+        lib.kkamd_par_ilut_filter.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64), ci, ci, vp]
+        lib.kkamd_par_ilut_residual.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(dbl), ci, ci, vp]
+        names += PAR_ILUT_EXPORTS
     if hasattr(lib, "kkamd_graph_d2_mis"):
         lib.kkamd_graph_d2_mis.argtypes = [i64, vp, ci, vp, ci, vp, C.POINTER(i64), C.POINTER(i64), vp]
         lib.kkamd_graph_mis2_aggregate.argtypes = [i64, vp, ci, vp, ci, vp, C.POINTER(i64), C.POINTER(i64), vp]

@@ -4685,6 +4685,10 @@ int kkamd_spgemm_set(kkamd_spgemm_handle_t* h, const char* key, double value) {
     h->compression_cutoff = value;
   } else if (k == "verbose") {
     h->verbose = value < 0 ? 0 : (int)value;          // 2: also host-side stage times of the symbolic phase (adds stream synchronisations)
+  } else if (k == "symbolic_computed") {
+    // 0: the next kkamd_spgemm_symbolic analyses again although it is given the row map arrays of the last call (a caller that rewrites
+    // its arrays in place with another pattern: ParILUT's L and U); 1 changes nothing
+    if (value == 0) { h->symbolic_called = false; h->numeric_called = false; h->entries_valid = false; h->rmA = nullptr; h->rmB = nullptr; }
   } else if (k == "entries_computed") {
     // the reference's SPGEMMHandle::are_entries_computed() as the caller sees it: 0 = entries(C) must be written again by the next
     // numeric call (the caller re-allocated or overwrote them); 1 = leave the decision to the handle (it keeps them only when it

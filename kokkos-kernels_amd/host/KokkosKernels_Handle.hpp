@@ -1,4 +1,4 @@
-// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV, SPILUK, Gauss-Seidel and GMRES paths use
+// KokkosKernels::Experimental::KokkosKernelsHandle -- the slice the SpGEMM, SPTRSV, SPILUK, Gauss-Seidel, GMRES and PAR_ILUT paths use
 // (reference: sparse/src/KokkosKernels_Handle.hpp:37-66,281-343,380-482, sptrsv :765-783,848-862, spiluk :853-870, gauss-seidel :538-544,581-628,
 // 715-720): create / get / destroy of the SpGEMM, SPTRSV, SPILUK and Gauss-Seidel sub-handles plus the tuning setters.  set_verbose acts (the library prints the chosen algorithm, row bins and compression
 // decision, like KOKKOSKERNELS_VERBOSE).  The team / vector / shared-memory / scheduling setters are HINTS in the reference
@@ -12,6 +12,7 @@
 #include "KokkosSparse_spiluk_handle.hpp"
 #include "KokkosSparse_gauss_seidel_handle.hpp"
 #include "KokkosSparse_gmres_handle.hpp"
+#include "KokkosSparse_par_ilut_handle.hpp"
 
 namespace KokkosKernels { namespace Experimental {
 
@@ -40,8 +41,10 @@ class KokkosKernelsHandle {
                                                                          PersistentMemorySpace>;
   using GMRESHandleType = KokkosSparse::Experimental::GMRESHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
                                                                  PersistentMemorySpace>;
+  using PAR_ILUTHandleType = KokkosSparse::Experimental::PAR_ILUTHandle<size_type, nnz_lno_t, nnz_scalar_t, ExecutionSpace, TemporaryMemorySpace,
+                                                                       PersistentMemorySpace>;
   KokkosKernelsHandle() = default;
-  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); destroy_gs_handle(); destroy_gmres_handle(); }
+  ~KokkosKernelsHandle() { destroy_spgemm_handle(); destroy_sptrsv_handle(); destroy_spiluk_handle(); destroy_gs_handle(); destroy_gmres_handle(); destroy_par_ilut_handle(); }
   KokkosKernelsHandle(const KokkosKernelsHandle&)            = delete;
   KokkosKernelsHandle& operator=(const KokkosKernelsHandle&) = delete;
 
@@ -99,6 +102,18 @@ class KokkosKernelsHandle {
   }
   void destroy_gmres_handle() { delete gmres_; gmres_ = nullptr; }
 
+  // PAR_ILUT sub-handle (:871-881, the reference's defaults); the hints given to this handle go to it as in the reference
+  PAR_ILUTHandleType* get_par_ilut_handle() { return par_ilut_; }
+  void create_par_ilut_handle(const size_type max_iter = 20, const typename PAR_ILUTHandleType::float_t residual_norm_delta_stop = 1e-2,
+                              const typename PAR_ILUTHandleType::float_t fill_in_limit = 0.75, const bool async_update = false,
+                              const bool verbose = false) {
+    destroy_par_ilut_handle();
+    par_ilut_ = new PAR_ILUTHandleType(max_iter, residual_norm_delta_stop, fill_in_limit, async_update, verbose);
+    par_ilut_->set_team_size(team_work_size);
+    par_ilut_->set_vector_size(vector_size);
+  }
+  void destroy_par_ilut_handle() { delete par_ilut_; par_ilut_ = nullptr; }
+
   // hints of the reference (:380-465; defaults :203-215): remembered, forwarded, without effect on gfx950
   void set_team_work_size(const int v) { team_work_size = v; hint("team_work_size", v); }
   int get_set_team_work_size() { return team_work_size; }
@@ -127,6 +142,7 @@ class KokkosKernelsHandle {
   SPILUKHandleType* spiluk_ = nullptr;
   PointGaussSeidelHandleType* gs_ = nullptr;
   GMRESHandleType* gmres_   = nullptr;
+  PAR_ILUTHandleType* par_ilut_ = nullptr;
   bool verbose_             = false;
 };
 

@@ -238,6 +238,16 @@ void deep_copy(const View<D1, P1...>& dst, const typename View<D1, P1...>::non_c
   Impl::check(hipMemcpy((void*)dst.data(), tmp.data(), n * sizeof(T), hipMemcpyDefault), "Kokkos::deep_copy(fill)");
 }
 
+// Kokkos::resize of a rank-1 view: a new allocation of n entries that keeps the leading min(old, n) of them
+template <class T, class... P>
+void resize(View<T*, P...>& v, size_t n) {
+  if (v.extent(0) == n) return;
+  View<T*, P...> w(v.label(), n);
+  const size_t keep = (v.extent(0) < n ? v.extent(0) : n) * sizeof(T);
+  if (keep) Impl::check(hipMemcpy((void*)w.data(), (const void*)v.data(), keep, hipMemcpyDefault), "Kokkos::resize");
+  v = w;
+}
+
 struct ALL_t {};
 inline ALL_t ALL() { return ALL_t(); }
 // column j of a rank-2 view as a (possibly strided) rank-1 view

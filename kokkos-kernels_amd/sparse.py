@@ -325,6 +325,7 @@ class KokkosKernelsHandle:
         self._spiluk = None
         self._gs = None
         self._gmres = None
+        self._par_ilut = None
 
     def create_spgemm_handle(self, algo="SPGEMM_KK"):
         """algo: a KokkosSparse::SPGEMMAlgorithm name (sparse/src/KokkosSparse_spgemm_handle.hpp:44-93).  SPGEMM_DEBUG / SPGEMM_SERIAL
@@ -374,6 +375,20 @@ class KokkosKernelsHandle:
         if self._spiluk is not None:
             self._spiluk.destroy()
         self._spiluk = None
+
+    def create_par_ilut_handle(self, max_iter=20, residual_norm_delta_stop=1e-2, fill_in_limit=0.75, async_update=False, verbose=False):
+        """create_par_ilut_handle(max_iter, residual_norm_delta_stop, fill_in_limit, async_update, verbose)
+        (sparse/src/KokkosKernels_Handle.hpp:871-881)"""
+        self.backend = self.backend or torch_backend()
+        self.destroy_par_ilut_handle()
+        self._par_ilut = _ParIlutHandle(self.backend, max_iter, residual_norm_delta_stop, fill_in_limit, async_update, verbose)
+
+    def get_par_ilut_handle(self): return self._par_ilut
+
+    def destroy_par_ilut_handle(self):
+        if self._par_ilut is not None:
+            self._par_ilut.destroy()
+        self._par_ilut = None
 
     def create_gs_handle(self, algo="GS_DEFAULT"):
         """create_gs_handle(GSAlgorithm) (sparse/src/KokkosKernels_Handle.hpp:581-628); algo: a KokkosSparse::GSAlgorithm name
@@ -559,6 +574,94 @@ def spiluk_numeric(kh, fill_lev, A_row_map, A_entries, A_values, L_row_map, L_en
         if e.status == _capi.ERR_STATE:
             raise ValueError(str(e))   # std::invalid_argument in the reference
         raise
+
+
+class _ParIlutHandle:
+    """KokkosSparse::Experimental::PAR_ILUTHandle (sparse/src/KokkosSparse_par_ilut_handle.hpp:55-200): the five inputs, nnzL / nnzU /
+    nrows of the symbolic phase, the statistics of the numeric phase, and this library's knob "lanes_per_row"."""
+
+    def __init__(self, backend, max_iter, residual_norm_delta_stop, fill_in_limit, async_update, verbose):
+        self.backend = backend
+        self.h = C.c_void_p()
+        check(backend.lib, backend.lib.kkamd_par_ilut_create(C.byref(self.h), int(max_iter), float(residual_norm_delta_stop), float(fill_in_limit),
+                                                             1 if async_update else 0, 1 if verbose else 0))
+
+    def set(self, key, value): check(self.backend.lib, self.backend.lib.kkamd_par_ilut_set(self.h, key.encode(), float(value)))
+
+    def get(self, key):
+        v = C.c_int64()
+        check(self.backend.lib, self.backend.lib.kkamd_par_ilut_get(self.h, key.encode(), C.byref(v)))
+        return int(v.value)
+
+    def get_real(self, key):
+        v = C.c_double()
+        check(self.backend.lib, self.backend.lib.kkamd_par_ilut_get_real(self.h, key.encode(), C.byref(v)))
+        return float(v.value)
+
+    def get_nrows(self): return self.get("num_rows")
+    def get_nnzL(self): return self.get("nnzL")
+    def get_nnzU(self): return self.get("nnzU")
+    def get_max_iter(self): return self.get("max_iter")
+    def set_max_iter(self, v): self.set("max_iter", v)
+    def get_residual_norm_delta_stop(self): return self.get_real("residual_norm_delta_stop")
+    def set_residual_norm_delta_stop(self, v): self.set("residual_norm_delta_stop", v)
+    def get_fill_in_limit(self): return self.get_real("fill_in_limit")
+    def set_fill_in_limit(self, v): self.set("fill_in_limit", v)
+    def get_async_update(self): return bool(self.get("async_update"))
+    def set_async_update(self, v): self.set("async_update", 1 if v else 0)
+    def get_verbose(self): return bool(self.get("verbose"))
+    def set_verbose(self, v): self.set("verbose", 1 if v else 0)
+    def get_num_iters(self): return self.get("num_iters")
+    def get_end_rel_res(self): return self.get_real("end_rel_res")
+    def is_symbolic_complete(self): return bool(self.get("symbolic_complete"))
+
+    def destroy(self):
+        if self.h:
+            self.backend.lib.kkamd_par_ilut_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def par_ilut_symbolic(kh, A_row_map, A_entries, L_row_map, U_row_map):
+    """KokkosSparse::Experimental::par_ilut_symbolic(handle, A_rowmap, A_entries, L_rowmap, U_rowmap) (sparse/src/KokkosSparse_par_ilut.hpp:76-190):
+    writes the row maps of the initial L and U and records nnzL, nnzU and the size in the handle."""
+    ih = _sub_handle(kh, "get_par_ilut_handle", "PAR_ILUT", "par_ilut_symbolic")
+    be, lib = ih.backend, ih.backend.lib
+    n = int(A_row_map.shape[0]) - 1
+    if L_row_map.shape[0] != n + 1 or U_row_map.shape[0] != n + 1:
+        raise RuntimeError("KokkosSparse::par_ilut_symbolic: L_rowmap and U_rowmap must have A_rowmap's extent %d" % (n + 1))
+    if _np_dtype(L_row_map) != _np_dtype(A_row_map) or _np_dtype(U_row_map) != _np_dtype(A_row_map):
+        raise RuntimeError("KokkosSparse::par_ilut_symbolic: A_rowmap, L_rowmap and U_rowmap must have one offset type")
+    check(lib, lib.kkamd_par_ilut_symbolic(ih.h, n, be.ptr(A_row_map), be.ptr(A_entries), be.ptr(L_row_map), be.ptr(U_row_map),
+                                           _offset_type(A_row_map), be.stream()))
+
+
+def par_ilut_numeric(kh, A_row_map, A_entries, A_values, L_row_map, U_row_map):
+    """KokkosSparse::Experimental::par_ilut_numeric (sparse/src/KokkosSparse_par_ilut.hpp:207-380).  The reference resizes the caller's
+    views; here the final row maps are written into L_row_map / U_row_map and the factors are returned as new arrays:
+    (L_entries, L_values, U_entries, U_values).  May be repeated with new values."""
+    ih = _sub_handle(kh, "get_par_ilut_handle", "PAR_ILUT", "par_ilut_numeric")
+    be, lib = ih.backend, ih.backend.lib
+    n = int(A_row_map.shape[0]) - 1
+    if _np_dtype(L_row_map) != _np_dtype(A_row_map) or _np_dtype(U_row_map) != _np_dtype(A_row_map):
+        raise RuntimeError("KokkosSparse::par_ilut_numeric: A_rowmap, L_rowmap and U_rowmap must have one offset type")
+    try:
+        check(lib, lib.kkamd_par_ilut_numeric(ih.h, n, be.ptr(A_row_map), be.ptr(A_entries), be.ptr(A_values), be.ptr(L_row_map), be.ptr(U_row_map),
+                                              _offset_type(A_row_map), _scalar_type(A_values), be.stream()))
+    except _capi.KkamdError as e:
+        if e.status == _capi.ERR_STATE:
+            raise ValueError(str(e))   # std::invalid_argument in the reference
+        raise
+    nl, nu = ih.get("nnzL_out"), ih.get("nnzU_out")
+    vdt = _np_dtype(A_values)
+    L_ent, L_val, U_ent, U_val = be.empty(nl, np.int32), be.empty(nl, vdt), be.empty(nu, np.int32), be.empty(nu, vdt)
+    check(lib, lib.kkamd_par_ilut_copy_factors(ih.h, be.ptr(L_ent), be.ptr(L_val), nl, be.ptr(U_ent), be.ptr(U_val), nu, be.stream()))
+    return L_ent, L_val, U_ent, U_val
 
 
 _GS_ALGOS = {"GS_DEFAULT": 0, "GS_PERMUTED": 1, "GS_TEAM": 2, "GS_CLUSTER": 3, "GS_TWOSTAGE": 4}
