@@ -31,6 +31,7 @@
 // the librccl.so.1 already in the process (torch's, MPI's or ROCm's: no second copy, no link-time dependency); a host
 // that communicates otherwise (MPI, or the gloo process group the CPU tests use) passes its own two functions.
 #include "kk_spmv_plan.h"
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <string>
@@ -272,8 +273,11 @@ static int dist_setup(kkamd_dist_spmv* op, int exchange, int overlap, hipStream_
   int h_mm[2] = {INT32_MAX, -1};
   KK_HIP(hipMemcpyAsync(mm.p, h_mm, sizeof h_mm, hipMemcpyHostToDevice, st));
   int* d_mm = mm.as<int>();
+  // the two kernels that scan the slab's entries stride over them: no more workgroups than there are entries to read, 1024 at most
+  // (both launches are guarded by nnz > 0, so there is at least one)
+  const unsigned scan_blocks = (unsigned)std::min<int64_t>(ceil_div(op->A.nnz, kBlock), 1024);
   if (op->A.nnz > 0) {
-    KK_LAUNCH(minmax_entries_kernel, 1024, kBlock, 0, st, (const int32_t*)op->A.d_entries, op->A.nnz, d_mm);
+    KK_LAUNCH(minmax_entries_kernel, scan_blocks, kBlock, 0, st, (const int32_t*)op->A.d_entries, op->A.nnz, d_mm);
     KK_LAUNCH_CHECK();
   }
   KK_HIP(hipMemcpyAsync(h_mm, mm.p, sizeof h_mm, hipMemcpyDeviceToHost, st));
@@ -307,7 +311,7 @@ static int dist_setup(kkamd_dist_spmv* op, int exchange, int overlap, hipStream_
     KK_HIP(hipMemsetAsync(flag.p, 0, (size_t)n, st));
     if (op->A.nnz > 0) {
       unsigned char* d_colflag = flag.as<unsigned char>();     // (the emulator's launch captures its arguments by value)
-      KK_LAUNCH(mark_offslab_cols_kernel, 1024, kBlock, 0, st, (const int32_t*)op->A.d_entries, op->A.nnz, (int)me0, (int)me1, d_colflag);
+      KK_LAUNCH(mark_offslab_cols_kernel, scan_blocks, kBlock, 0, st, (const int32_t*)op->A.d_entries, op->A.nnz, (int)me0, (int)me1, d_colflag);
       KK_LAUNCH_CHECK();
     }
     std::vector<unsigned char> h_flag((size_t)n);
